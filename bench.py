@@ -2,6 +2,7 @@
 """bench.py -- frames/s of the MI355X hot path (BASELINE.json metric) on N GPUs of one node.
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR               (also writes the last timed step's outputs as DIR/<name>.npy)
 
 A "step" is one pass of the hot path over `--batch` (default 8) 1024x1024 frames per rank (weak
 scaling: every rank owns its own frames, 8 per rank = BASELINE configs[3]'s 64 frames on 8 GPUs;
@@ -39,6 +40,9 @@ def parse():
     ap.add_argument("--no-iou", action="store_true", help="skip the one-frame mask IoU against the CPU oracle (about 20 s of host time, untimed)")
     ap.add_argument("--no-roofline", action="store_true", help="profiling runs: skip the per-op HIP-event pass, so that the process executes "
                                                                "exactly 1 + warmup + steps steps (rocprofv3 totals divide cleanly)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                                                          "(float32 / float64, at most 64 MB; a seeded sample of pixels when the "
+                                                          "full outputs would not fit) so that two builds can be compared output for output")
     ap.add_argument("--cpu-seconds", type=float, default=90.0, help="budget of the host-side oracle run (full-size nets; stages that "
                                                                     "would not fit are scaled from the measured GFLOP/s and say so)")
     return ap.parse_args()
@@ -121,6 +125,28 @@ class Workload:
     def extra(self):
         return {}
 
+    def outputs(self, last):
+        """host arrays of what a caller of the timed path holds after the step that returned `last`: the uint8 frames [F, H, W, 3],
+        the instance masks [F, MAX_INST, H, W] (zero planes past a frame's count) and the instance counts [F], decoded from the
+        output records (rank 0 of a multi-rank run: every rank's records of that step, rank-major); None on the other ranks"""
+        from cartoonsegmentation_amd import shard
+        if self.dist is None:
+            recs = self.records[:self.frames_per_step]
+        elif self.gather_list is not None:
+            recs = torch.cat(self.gather_list)
+        else:
+            return None
+        frames, masks, counts = [], np.zeros((len(recs), self.MAX_INST, self.H, self.W), np.bool_), []
+        for k, rec in enumerate(recs):
+            frame, m, n = shard.read_record(rec, self.H, self.W, self.MAX_INST)
+            frames.append(frame.numpy())
+            masks[k, :m.shape[0]] = m.numpy()
+            counts.append(n)
+        out = {"frames": np.stack(frames), "instance_counts": np.asarray(counts)}
+        if self.MAX_INST:
+            out["masks"] = masks
+        return out
+
 
 class WarpWorkload(Workload):
     """process_shift -> render_pointcloud(C=4) -> fill_disocclusion -> uint8 (kenburns_effect.py:1027-1040)"""
@@ -151,6 +177,11 @@ class WarpWorkload(Workload):
         if self.dist is not None:
             self.frame_slot(0).copy_(frame)
         return frame
+
+    def outputs(self, last):
+        if self.dist is None:                # one process: the frame step() returned (the records are filled for the gather only)
+            return {"frames": last.cpu().numpy()[None]}
+        return super().outputs(last)
 
     def config(self, world):
         return {"workload": "warp-only: process_shift+render_pointcloud(C=4,N=P)+fill_disocclusion+uint8, %dx%d"
@@ -755,6 +786,43 @@ def load_traffic(kernel_key):
     return None
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir, seed=0):
+    """write the timed path's outputs (Workload.outputs) as out_dir/<name>.npy: integer and boolean arrays as float32 (exact),
+    plus float64 whole-output sums (frame_channel_sums [F, 3], mask_areas [F, MAX_INST]) that see every pixel.  When the per-pixel
+    arrays would pass DUMP_BYTES, frames [F, K, 3] and masks [F, MAX_INST, K] hold K pixels drawn with a fixed seed (the same K
+    for every frame and mask; pixel_index [K] = y * W + x, float64) instead of [F, H, W, 3] and [F, MAX_INST, H, W].
+    -> {name: shape} of the files written"""
+    frames, masks = arrays["frames"], arrays.get("masks")
+    F, H, W, _ = frames.shape
+    out = {"instance_counts": arrays["instance_counts"].astype(np.float64) if "instance_counts" in arrays else None,
+           "frame_channel_sums": frames.reshape(F, -1, 3).sum(1, dtype=np.float64)}
+    if masks is not None:
+        out["mask_areas"] = masks.reshape(F, masks.shape[1], -1).sum(2, dtype=np.float64)
+    per_pixel = 4 * F * (3 + (0 if masks is None else masks.shape[1]))           # float32 bytes of one pixel position
+    fixed = sum(v.nbytes for v in out.values() if v is not None)
+    if per_pixel * H * W + fixed <= DUMP_BYTES:
+        out["frames"] = frames.astype(np.float32)
+        if masks is not None:
+            out["masks"] = masks.astype(np.float32)
+    else:
+        K = (DUMP_BYTES - fixed - (8 << 20)) // (per_pixel + 8)       # 8 MB of headroom below the cap
+        idx = np.sort(np.random.default_rng(seed).choice(H * W, size=K, replace=False))
+        out["pixel_index"] = idx.astype(np.float64)
+        out["frames"] = frames.reshape(F, H * W, 3)[:, idx].astype(np.float32)
+        if masks is not None:
+            out["masks"] = masks.reshape(F, masks.shape[1], H * W)[:, :, idx].astype(np.float32)
+    out = {k: v for k, v in out.items() if v is not None}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_BYTES, "output dump of %d bytes exceeds %d" % (total, DUMP_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in out.items()}
+
+
 def main():
     a = parse()
     if os.environ.get("CSM_BENCH_WATCHDOG"):          # debugging aid: dump every thread's stack and exit after N seconds
@@ -833,7 +901,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        wl.step_and_gather()
+        last = wl.step_and_gather()
     wl.finish_gathers()                                # every step's frames are on rank 0 before the clock stops
     torch.cuda.synchronize()
     if dist is not None:
@@ -843,6 +911,11 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if a.dump_outputs:                  # before anything below runs the workload again and overwrites the last step's outputs
+        arrays = wl.outputs(last)
+        if arrays is not None:
+            dumped = dump_outputs(arrays, a.dump_outputs)
 
     out = None
     if rank == 0:
@@ -852,6 +925,8 @@ def main():
                "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": wl.dtype, "data": "synthetic",
                "config": wl.config(world)}
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         out["roofline"] = None if a.no_roofline else wl.roofline()
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = wl.cpu_baseline(a.cpu_seconds)

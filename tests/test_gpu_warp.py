@@ -20,6 +20,12 @@ RENDER_CASES = sorted(p for p in glob.glob(os.path.join(GOLDEN, "warp_*.npz")) i
 IDS = [os.path.basename(p)[:-4] for p in RENDER_CASES]
 
 
+def cases(keep):
+    """(paths, ids) of the render fixtures whose file name passes `keep` (the name only: the checkout's directory may hold any text)"""
+    sel = [(p, i) for p, i in zip(RENDER_CASES, IDS) if keep(i)]
+    return dict(argvalues=[p for p, _ in sel], ids=[i for _, i in sel])
+
+
 @pytest.fixture(scope="module")
 def ops():
     assert torch.cuda.is_available(), "gpu tests need an MI355X"
@@ -83,7 +89,7 @@ def test_render_pointcloud(ops, path, how):
     assert ok[agree].mean() >= 0.999
 
 
-@pytest.mark.parametrize("path", [p for p in RENDER_CASES if 'c4' in p], ids=[i for i in IDS if 'c4' in i])
+@pytest.mark.parametrize("path", **cases(lambda i: 'c4' in i))
 def test_fill_disocclusion_bit_exact(ops, path):
     g = dict(np.load(path))
     out = ops.fill_disocclusion(dev(g['render']), dev(g['fill_depth'])).cpu().numpy()
@@ -246,7 +252,7 @@ def test_edge_cases(ops):
         ops.render_pointcloud(torch.zeros(1, 3, 4), torch.zeros(1, 2, 4), W, H, 15.0, 40.0)   # CPU tensors: no fallback
 
 
-@pytest.mark.parametrize("path", [p for p in RENDER_CASES if 'c4' in p and 'b2' not in p], ids=[i for i in IDS if 'c4' in i and 'b2' not in i])
+@pytest.mark.parametrize("path", **cases(lambda i: 'c4' in i and 'b2' not in i))
 def test_frame_inside_fma_bracket(ops, path):
     """the fused frame kernel vs BOTH ends of the FMA-contraction bracket (fixtures built with -ffp-contract=off and =fast):
     the z-buffer equals both bit for bit, every uint8 value is within one level of one of them wherever the degrid orders agree"""
