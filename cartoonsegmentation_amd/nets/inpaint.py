@@ -3,8 +3,9 @@
   context : netContext on cat(normalised image, normalised disparity)            (:82-87, :133)
   grid    : netInput + 4x4 GridNet + netImage / netDisparity on cat(render, existing)  (:89-110, :147-190)
 The forward splat between them (render_pointcloud with C=68, :135), the median-5 mask clean-up (:141) and the
-mean/std (de)normalisation are operators / scalar glue in kenburns.py.  H and W must be multiples of 8 (the
-reference crops odd up-sampled maps with a negative pad, :170-171; not needed at the benchmark sizes)."""
+mean/std (de)normalisation are operators / scalar glue in kenburns.py.  Any H and W: where the x2-up-sampled row below is one
+row / column larger than the row it joins (an odd size on the way down), the reference drops its last row / column with a negative
+pad (:165-166, :178-179); the lowering crops it in a separate add (Program.add), and fuses the add into the conv epilogue elsewhere."""
 from ..program import Program
 from ..weights import conv_plain
 from .gridblocks import basic, downsample, upsample
@@ -27,8 +28,6 @@ def build_inpaint_context(ws, H, W):
 
 
 def build_inpaint_grid(ws, H, W):
-    if H % 8 or W % 8:
-        raise NotImplementedError("Inpaint GridNet: H and W must be multiples of 8 (odd-size crop path not built)")
     p = Program("inpaint_grid")
     x_ext = p.ext_nchw(1, 69, H, W)
     img_ext = p.ext_nchw(1, 3, H, W)
@@ -44,7 +43,15 @@ def build_inpaint_grid(ws, H, W):
     for c in (2, 3):
         for r in range(3, -1, -1):
             lat = basic(p, ws, '%dx%d - %dx%d' % (r, c - 1, r, c), 'relu-conv-relu-conv', (ROWS[r],) * 3, col[r])
-            col[r] = lat if r == 3 else upsample(p, ws, '%dx%d - %dx%d' % (r + 1, c, r, c), (ROWS[r + 1], ROWS[r], ROWS[r]), col[r + 1], res=lat)
+            if r == 3:
+                col[r] = lat
+                continue
+            below = col[r + 1]
+            if below.h * 2 == lat.h and below.w * 2 == lat.w:
+                col[r] = upsample(p, ws, '%dx%d - %dx%d' % (r + 1, c, r, c), (ROWS[r + 1], ROWS[r], ROWS[r]), below, res=lat)
+            else:                                                  # pad [0,0,0,-1] / [0,-1,0,0]: drop the last row / column of the up-sampled map
+                up = upsample(p, ws, '%dx%d - %dx%d' % (r + 1, c, r, c), (ROWS[r + 1], ROWS[r], ROWS[r]), below)
+                col[r] = p.add(up, lat)
     im = basic(p, ws, 'netImage', 'conv-relu-conv', (32, 32, 3), col[0])
     ds = basic(p, ws, 'netDisparity', 'conv-relu-conv', (32, 32, 1), col[0])
     p.to_nchw(im, img_ext)

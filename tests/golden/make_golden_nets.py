@@ -74,12 +74,15 @@ def leres_cases():
         print('leres', tag, float(y.mean()), float(y.std()))
 
 
-def inpaint_case():
-    """whole Inpaint.forward of the reference (incl. its render_pointcloud CUDA text through cuda_on_cpu.h)"""
+INPAINT_SIZES = ((32, 40), (35, 45), (36, 44), (33, 40), (27, 61))
+
+
+def inpaint_case(H, W):
+    """whole Inpaint.forward of the reference (incl. its render_pointcloud CUDA text through cuda_on_cpu.h) at H x W; the sizes
+    other than 32x40 take the odd-size crops of pointcloud_inpainting.py:165-166, :178-179 at one or more joins"""
     mu, co, cu = ref_loader.load_warp_modules()
     m = ref_loader.load_by_path("anime_3dkenburns.models.pointcloud_inpainting", "anime_3dkenburns/models/pointcloud_inpainting.py")
     net = fill_synthetic(m.Inpaint(), 'inpaint.')
-    H, W = 32, 40
     g = np.random.default_rng(77)
     img = g.uniform(0, 1, (1, 3, H, W)).astype(np.float32)
     yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
@@ -90,10 +93,10 @@ def inpaint_case():
     common = {'fltFocal': W / 2.0, 'fltBaseline': 40.0, 'intWidth': W, 'intHeight': H}
     with torch.no_grad():
         out = net(torch.from_numpy(img), torch.from_numpy(disp.astype(np.float32)), torch.from_numpy(shift), common, torch.from_numpy(seg))
-    np.savez_compressed(os.path.join(HERE, 'net_inpaint_32x40.npz'), img=img, disp=disp.astype(np.float32), shift=shift, seg=seg,
+    np.savez_compressed(os.path.join(HERE, 'net_inpaint_%dx%d.npz' % (H, W)), img=img, disp=disp.astype(np.float32), shift=shift, seg=seg,
                         existing=out['tenExisting'].numpy(), image=out['tenImage'].numpy(), disparity=out['tenDisparity'].numpy(),
                         segmasks=out['segmasks'].numpy())
-    print('inpaint', float(out['tenExisting'].mean()), float(out['tenImage'].mean()), float(out['tenDisparity'].mean()))
+    print('inpaint %dx%d' % (H, W), float(out['tenExisting'].mean()), float(out['tenImage'].mean()), float(out['tenDisparity'].mean()))
 
 
 def refine_case():
@@ -305,7 +308,8 @@ if __name__ == '__main__':
     if 'leres' in which:
         leres_cases()
     if 'inpaint' in which:
-        inpaint_case()
+        for h, w in INPAINT_SIZES:
+            inpaint_case(h, w)
     if 'refine' in which:
         refine_case()
     if 'zoe_infer' in which:

@@ -458,3 +458,29 @@ def test_bilinear_row_kernel_bit_exact(n, h, w, c, ho, wo, align):
     p.to_nchw(y, y_ext)
     (yo,), (yd,) = run_both(p, [rnd('bilx%d%d%d%d' % (n, h, w, c), (n, c, h, w))], [(n, c, ho, wo)])
     assert np.isfinite(yd).all() and np.array_equal(yo, yd)
+
+
+# H, W, OP_ADD count (the cropped joins of pointcloud_inpainting.py:165-166, :178-179): the reference-module fixture sizes, frames
+# that scaledown_maxsize(1024) makes of ordinary photos (1680x1359 -> 828x1024, 1000x750 -> 750x1000) and an odd x odd one, where
+# F(4x4) Winograd tiles run ragged on odd-sized maps that meet the cropped add; 1080x720 halves evenly (fused joins only)
+INPAINT_GRID_SIZES = [(32, 40, 0), (35, 45, 6), (36, 44, 2), (33, 40, 6), (27, 61, 6), (828, 1024, 2), (517, 333, 4), (750, 1000, 2),
+                      (1080, 720, 0)]
+
+
+@pytest.mark.parametrize("H,W,n_add", INPAINT_GRID_SIZES, ids=["%dx%d" % c[:2] for c in INPAINT_GRID_SIZES])
+def test_inpaint_grid_bit_exact(H, W, n_add):
+    """the Inpaint GridNet program (build_inpaint_grid, shipped Winograd rule) on the HIP engine vs the oracle interpreter on one seeded
+    69-channel input: bit-exact, like every lowered net here"""
+    from cartoonsegmentation_amd.nets import build_inpaint_grid
+    from cartoonsegmentation_amd.program import OP_ADD, OP_CONV
+    prog = build_inpaint_grid(SynthWeights('inpaint.'), H, W)
+    adds = [o for o in prog.ops if o['kind'] == OP_ADD]
+    n_w4 = sum(1 for o in prog.ops if o['kind'] == OP_CONV and o['flags'] & 8)
+    assert len(adds) == n_add
+    if (H, W) == (828, 1024):
+        assert n_w4 > 0 and n_add > 0, "the operating shape must meet F(4x4) convolutions and the cropped add in one program"
+    x = np.random.default_rng(H * 10007 + W).normal(0, 1, (1, 69, H, W)).astype(np.float32)
+    (io, do), (idv, ddv) = run_both(prog, [x], [(1, 3, H, W), (1, 1, H, W)])
+    print("inpaint grid %dx%d: %d F(4x4) convs, %d cropped adds, |image| max %.3g" % (H, W, n_w4, n_add, float(np.abs(io).max())))
+    assert np.abs(io).max() > 0 and np.isfinite(idv).all() and np.isfinite(ddv).all()
+    assert np.array_equal(io, idv) and np.array_equal(do, ddv)

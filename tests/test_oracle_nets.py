@@ -90,24 +90,77 @@ def test_refine_vs_reference_module():
     assert rel_err(r, g['y']) < 1e-4
 
 
-def test_inpaint_forward_vs_reference():
+# fixture size -> number of OP_ADD ops of its grid program: one per x2-up-sampled map that is cropped (columns 2 and 3 each have three
+# joins, rows 3->2, 2->1, 1->0); 32x40 halves evenly down to 4x5 and fuses every join into the conv epilogue
+INPAINT_CASES = [(32, 40, 0), (35, 45, 6), (36, 44, 2), (33, 40, 6), (27, 61, 6)]
+
+
+@pytest.mark.parametrize("H,W,n_add", INPAINT_CASES, ids=["%dx%d" % c[:2] for c in INPAINT_CASES])
+def test_inpaint_forward_vs_reference(H, W, n_add):
     """whole Inpaint.forward: context conv -> C=68 splat -> median-5 -> GridNet (reference fixture runs the
-    reference's own CUDA text sequentially)"""
+    reference's own CUDA text sequentially); the odd sizes take the reference's negative-pad crops (pointcloud_inpainting.py:165-166,
+    :178-179) at the joins where the up-sampled row below is one row / column larger"""
     from cartoonsegmentation_amd.nets import build_inpaint_context, build_inpaint_grid
+    from cartoonsegmentation_amd.program import OP_ADD
     from oracle import kenburns as okb
-    g = dict(np.load(os.path.join(GOLDEN, "net_inpaint_32x40.npz")))
-    H, W = 32, 40
+    g = dict(np.load(os.path.join(GOLDEN, "net_inpaint_%dx%d.npz" % (H, W))))
+    assert g['img'].shape == (1, 3, H, W)
     ws = SynthWeights('inpaint.')
     ctx, grid = build_inpaint_context(ws, H, W), build_inpaint_grid(ws, H, W)
+    assert sum(1 for o in grid.ops if o['kind'] == OP_ADD) == n_add
     # degrid_mode 0 = the in-place pass the fixture was produced with (sequential execution of the reference text)
     o = okb.inpaint_forward(g['img'], g['disp'], g['shift'], g['seg'], W, H, W / 2.0, 40.0, ctx, grid, degrid_mode=0)
     assert np.array_equal(o['existing'], g['existing'])
-    assert np.array_equal(o['segmasks'], g['segmasks'])
+    # segmasks channels 0-2 splat the instance masks: exact.  Channel 3 splats the normalised disparity, whose mean / std the oracle
+    # takes in float64 and torch in float32: the two normalisations agree bit for bit at 32x40 only by luck of that shape, so the other
+    # sizes hold channel 3 to 1e-6 of its maximum (fp32 rounding of the statistics: measured <= 7.2e-7 on a maximum of 2.7)
+    assert np.array_equal(o['segmasks'][:, :3], g['segmasks'][:, :3])
+    if (H, W) == (32, 40):
+        assert np.array_equal(o['segmasks'], g['segmasks'])
+    else:
+        assert np.abs(o['segmasks'][:, 3] - g['segmasks'][:, 3]).max() <= 1e-6 * np.abs(g['segmasks'][:, 3]).max()
     assert np.abs(o['image'] - g['image']).max() < 1e-4
     assert np.abs(o['disparity'] - g['disparity']).max() / g['disparity'].max() < 1e-4
     # Jacobi degrid (the HIP build's deterministic semantics): same coverage except a handful of pixels
     o1 = okb.inpaint_forward(g['img'], g['disp'], g['shift'], g['seg'], W, H, W / 2.0, 40.0, ctx, grid, degrid_mode=1)
     assert (o1['existing'] == g['existing']).mean() > 0.99
+
+
+def _inpaint_grid_fused_only(ws, H, W):
+    """the Inpaint GridNet as lowered before the odd-size crop existed: every up-sampling join fused into the conv epilogue"""
+    from cartoonsegmentation_amd.nets.gridblocks import basic, downsample, upsample
+    from cartoonsegmentation_amd.nets.inpaint import ROWS
+    from cartoonsegmentation_amd.program import Program
+    p = Program("inpaint_grid")
+    x_ext = p.ext_nchw(1, 69, H, W)
+    img_ext, dsp_ext = p.ext_nchw(1, 3, H, W), p.ext_nchw(1, 1, H, W)
+    col = [basic(p, ws, 'netInput', 'conv-relu-conv', (69, 32, 32), p.to_nhwc(x_ext))]
+    for r in range(1, 4):
+        col.append(downsample(p, ws, '%dx0 - %dx0' % (r - 1, r), (ROWS[r - 1], ROWS[r], ROWS[r]), col[r - 1]))
+    for r in range(4):
+        lat = basic(p, ws, '%dx0 - %dx1' % (r, r), 'relu-conv-relu-conv', (ROWS[r],) * 3, col[r])
+        col[r] = lat if r == 0 else downsample(p, ws, '%dx1 - %dx1' % (r - 1, r), (ROWS[r - 1], ROWS[r], ROWS[r]), col[r - 1], res=lat)
+    for c in (2, 3):
+        for r in range(3, -1, -1):
+            lat = basic(p, ws, '%dx%d - %dx%d' % (r, c - 1, r, c), 'relu-conv-relu-conv', (ROWS[r],) * 3, col[r])
+            col[r] = lat if r == 3 else upsample(p, ws, '%dx%d - %dx%d' % (r + 1, c, r, c), (ROWS[r + 1], ROWS[r], ROWS[r]), col[r + 1], res=lat)
+    im = basic(p, ws, 'netImage', 'conv-relu-conv', (32, 32, 3), col[0])
+    ds = basic(p, ws, 'netDisparity', 'conv-relu-conv', (32, 32, 1), col[0])
+    p.to_nchw(im, img_ext)
+    p.to_nchw(ds, dsp_ext)
+    p.plan()
+    return p
+
+
+@pytest.mark.parametrize("H,W", [(1024, 1024), (1080, 720), (32, 40)])
+def test_inpaint_grid_unchanged_at_sizes_that_halve_evenly(H, W):
+    """at sizes that are multiples of 8 the odd-size crop never fires: the program (op kinds, execution-form flags, shapes) is the
+    fused-only lowering, so the benchmark's inpaint programs do not move"""
+    from cartoonsegmentation_amd.nets import build_inpaint_grid
+    ws = SynthWeights('inpaint.')
+    got, want = build_inpaint_grid(ws, H, W), _inpaint_grid_fused_only(ws, H, W)
+    assert [(o['kind'], o['flags']) for o in got.ops] == [(o['kind'], o['flags']) for o in want.ops]
+    assert got.ops == want.ops
 
 
 @pytest.mark.parametrize("tag,h,w", [("96x64", 96, 64), ("64x128", 64, 128), ("72x88", 72, 88)])
