@@ -6,17 +6,14 @@
 //                   then cv2.resize(INTER_AREA) back to the frame size and zero-fix (kenburns_effect.py:572-578)
 //   * frame tail  : cv2.getRectSubPix + cv2.resize(INTER_LINEAR) (kenburns_effect.py:1069-1070)
 #include "csm_common.h"
+#include "csm_resample.h"
 
 namespace {
 
-__device__ __forceinline__ void cv_src(int d, int in_size, double scale, int &i0, int &i1, float &f) {
-    float fx = (float)((d + 0.5) * scale - 0.5);
-    int sx = (int)floorf(fx);
-    fx -= (float)sx;
-    if (sx < 0) { fx = 0.0f; sx = 0; }
-    if (sx >= in_size - 1) { fx = 0.0f; sx = in_size - 1; }
-    i0 = sx; i1 = min(sx + 1, in_size - 1); f = fx;
-}
+using csmimg::cv_src;
+using csmimg::cv_lin_u8;
+using csmimg::cv_lin_f32;
+
 // INTER_AREA when up-sampling: linear taps with "area" fractions (resize.cpp, area_mode branch)
 __device__ __forceinline__ void cv_src_area(int d, int in_size, double scale, int &i0, int &i1, float &f) {
     int sx = (int)floor(d * scale);
@@ -25,13 +22,6 @@ __device__ __forceinline__ void cv_src_area(int d, int in_size, double scale, in
     if (sx < 0) { fx = 0.0f; sx = 0; }
     if (sx >= in_size - 1) { fx = 0.0f; sx = in_size - 1; }
     i0 = sx; i1 = min(sx + 1, in_size - 1); f = fx;
-}
-__device__ __forceinline__ int cv_lin_u8(int p00, int p01, int p10, int p11, float fx, float fy) {
-    const int a0 = (int)rintf((1.0f - fx) * 2048.0f), a1 = (int)rintf(fx * 2048.0f);
-    const int b0 = (int)rintf((1.0f - fy) * 2048.0f), b1 = (int)rintf(fy * 2048.0f);
-    int r0 = p00 * a0 + p01 * a1, r1 = p10 * a0 + p11 * a1;
-    int q = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-    return q < 0 ? 0 : (q > 255 ? 255 : q);
 }
 
 struct Norm3 { float mean[3], stdv[3]; };
@@ -326,12 +316,9 @@ __global__ __launch_bounds__(256) void k_resize_f32_linear(const float *__restri
     if (x >= w) return;
     int y0, y1, x0, x1; float fy, fx;
     cv_src(y, H, (double)H / h, y0, y1, fy); cv_src(x, W, (double)W / w, x0, x1, fx);
-    const float a0 = 1.0f - fx, a1 = fx, b0 = 1.0f - fy, b1 = fy;
-    for (int c = 0; c < C; ++c) {
-        const float r0 = src[((int64_t)y0 * W + x0) * C + c] * a0 + src[((int64_t)y0 * W + x1) * C + c] * a1;
-        const float r1 = src[((int64_t)y1 * W + x0) * C + c] * a0 + src[((int64_t)y1 * W + x1) * C + c] * a1;
-        dst[((int64_t)y * w + x) * C + c] = r0 * b0 + r1 * b1;
-    }
+    for (int c = 0; c < C; ++c)
+        dst[((int64_t)y * w + x) * C + c] = cv_lin_f32(src[((int64_t)y0 * W + x0) * C + c], src[((int64_t)y0 * W + x1) * C + c],
+                                                       src[((int64_t)y1 * W + x0) * C + c], src[((int64_t)y1 * W + x1) * C + c], fx, fy);
 }
 
 extern "C" int csm_resize_f32_linear(const float *src_hwc, int H, int W, int C, int h, int w, float *dst_hwc, void *stream) {

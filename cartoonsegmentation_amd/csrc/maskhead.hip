@@ -7,24 +7,12 @@
 //     sigmoid -> crop -> bilinear(align_corners=True) -> threshold (:653-662).
 // All HBM-bound: the only large traffic is the n x H x W byte masks, written once, coalesced.
 #include "csm_common.h"
+#include "csm_resample.h"
 
 namespace {
 
-__device__ __forceinline__ float csm_expf(float x) {   // same polynomial as nets.hip / DESIGN.md
-    x = fminf(fmaxf(x, -87.0f), 88.0f);
-    float n = rintf(x * 1.44269504088896341f);
-    float r = fmaf(n, -0.693145751953125f, x);
-    r = fmaf(n, -1.42860682030941723212e-6f, r);
-    float p = 1.9875691500e-4f;
-    p = fmaf(p, r, 1.3981999507e-3f);
-    p = fmaf(p, r, 8.3334519073e-3f);
-    p = fmaf(p, r, 4.1665795894e-2f);
-    p = fmaf(p, r, 1.6666665459e-1f);
-    p = fmaf(p, r, 5.0000001201e-1f);
-    float e = fmaf(p, r * r, r) + 1.0f;
-    return e * __int_as_float(((int)n + 127) << 23);
-}
-__device__ __forceinline__ float csm_sigmoid(float v) { return 1.0f / (1.0f + csm_expf(-v)); }
+using csmimg::csm_sigmoid;
+using csmimg::cv_src;
 
 // aten upsample_bilinear2d source index (same rule as nets.hip)
 __device__ __forceinline__ void src_index(int dst, int in_size, int out_size, float scale, bool align, int &i0, int &i1,
@@ -187,16 +175,6 @@ __global__ __launch_bounds__(256) void k_refine_threshold(const float *__restric
     float p10 = csm_sigmoid(L[y1 * S_w + x0]), p11 = csm_sigmoid(L[y1 * S_w + x1]);
     float v = hl0 * (wl0 * p00 + wl1 * p01) + hl1 * (wl0 * p10 + wl1 * p11);
     out[((int64_t)inst * oh + oy) * ow + ox] = v > thr ? 1 : 0;
-}
-
-// cv2.resize(INTER_LINEAR) source coordinate (half-pixel centres, clamped)  [EXT: OpenCV 4.10 resize.cpp]
-__device__ __forceinline__ void cv_src(int d, int in_size, double scale, int &i0, int &i1, float &f) {
-    float fx = (float)((d + 0.5) * scale - 0.5);
-    int sx = (int)floorf(fx);
-    fx -= (float)sx;
-    if (sx < 0) { fx = 0.0f; sx = 0; }
-    if (sx >= in_size - 1) { fx = 0.0f; sx = in_size - 1; }
-    i0 = sx; i1 = min(sx + 1, in_size - 1); f = fx;
 }
 
 // prepare_refine_batch (animeinsseg/__init__.py:37-55): img u8 HWC [H,W,3] -> resize_pad to T (keep ratio, pad

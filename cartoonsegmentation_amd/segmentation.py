@@ -5,6 +5,8 @@ Flow per image (reference :464-504, :447-462, :638-665), everything on the MI355
   uint8 image --csm_det_preprocess--> RTMDet-Ins layer program --csm_det_decode--> csm_nms --csm_det_gather-->
   csm_maskhead_logits --> csm_mask_resize_threshold --> [ISNet refine: csm_refine_prepare_batch --> ISNet layer
   program --> csm_refine_threshold] --> AnimeInstances(masks bool [n,H,W], bboxes xywh int32, scores).
+refine_method='animeseg' (reference :78-115, :623-630) instead runs the anime-seg ISNet-IS over the frame:
+  csm_animeseg_prepare --> ISNetDIS(in_ch=3) layer program --> csm_animeseg_mask (fg) --> csm_animeseg_select (in place).
 The reference makes 5 host<->device crossings per image; here the only syncs are the data-dependent counts.
 
 Checkpoints: a real `rtmdetl_e60.ckpt` (mmdet state_dict + cfg text) and `refine_last.ckpt` import through
@@ -26,7 +28,8 @@ from .nets import RTMDetConfig, build_isnet, build_rtmdet
 from .runtime import CompiledProgram
 from .weights import StateDictWeights, SynthWeights
 
-VALID_REFINEMETHODS = {'refinenet_isnet', 'none'}
+VALID_REFINEMETHODS = {'refinenet_isnet', 'animeseg', 'none'}
+ANIMESEG_CKPT = 'models/anime-seg/isnetis.ckpt'                 # animeinsseg/models/animeseg_refine/__init__.py:158
 
 
 def rescale_size(h, w, scale):
@@ -45,6 +48,39 @@ def scaledown_size(h, w, max_size):
         else:
             w, h = max_size, max(1, int(round(h * r)))
     return h, w
+
+
+def animeseg_size(h0, w0, s):
+    """get_mask letterbox rule (animeinsseg/models/animeseg_refine/__init__.py:170-174): long side s, short side
+    int(s * short / long) -- Python float division, then truncation."""
+    if h0 > w0:
+        h, w = s, int(s * w0 / h0)
+    else:
+        h, w = int(s * h0 / w0), s
+    if h < 1 or w < 1:
+        raise _lib.CsmError("animeseg refine: a %dx%d frame letterboxes to %dx%d at size %d (aspect ratio too extreme)" % (h0, w0, h, w, s))
+    return h, w
+
+
+def animeseg_state_dict(blob):
+    """the three layouts AnimeSegmentation.try_load accepts (animeseg_refine/__init__.py:75-85) -> ISNetDIS parameter names:
+    a Lightning checkpoint ('epoch' present, weights under 'state_dict'), a flat AnimeSegmentation state dict ('net.*' and
+    'gt_encoder.*' keys), or a bare ISNetDIS state dict.  'net.' is stripped; the training-only gt_encoder is dropped."""
+    sd = blob['state_dict'] if 'epoch' in blob else blob
+    if any(k.startswith('net.') for k in sd):
+        sd = {k[4:]: v for k, v in sd.items() if k.startswith('net.')}
+    return sd
+
+
+def load_animeseg_weights(ckpt=None, synthetic=False):
+    """StateDictWeights of the anime-seg ISNet-IS checkpoint, or the closed-form SynthWeights('animeseg.') when the file is
+    absent and synthetic weights are allowed"""
+    ckpt = ckpt or ANIMESEG_CKPT
+    if os.path.exists(ckpt):
+        return StateDictWeights(animeseg_state_dict(torch.load(ckpt, map_location='cpu', weights_only=False)))
+    if not synthetic:
+        raise FileNotFoundError(ckpt)
+    return SynthWeights('animeseg.')
 
 
 def _parse_mm_cfg(text):
@@ -108,6 +144,7 @@ class AnimeInsSeg:
             self._det_ws = StateDictWeights(blob['state_dict'])
         self._det_programs, self._det_weights = {}, {}          # (weights: packed images on the device by packing signature)
         self._refine_programs, self._refine_weights, self._refine_ws = {}, {}, None
+        self._animeseg_programs, self._animeseg_weights, self._animeseg_ws = {}, {}, None
         self.refine_method = None
         self.refine_batch = int(os.environ.get('CSM_REFINE_BATCH', '16'))   # instances per ISNet run when frames are batched
         self.det_batch = max(1, int(os.environ.get('CSM_DET_BATCH', '16')))  # frames per detector run (longer lists are chunked)
@@ -118,11 +155,12 @@ class AnimeInsSeg:
         self.default_det_size = det_size if isinstance(det_size, int) else max(det_size)
 
     def set_refine_method(self, refine_method: str = 'none', refine_size: int = 720, refinenet_ckpt: str = None, **kw):
-        if refine_method == 'animeseg':
-            raise NotImplementedError("refine_method 'animeseg' is out of the hot-path scope (SURVEY 2.1)")
         if refine_method not in VALID_REFINEMETHODS:
             raise NotImplementedError('Invalid refine method: %s' % refine_method)
         self.refine_method, self.refine_size = refine_method, refine_size
+        if refine_method == 'animeseg' and self._animeseg_ws is None:
+            synthetic = str(self.ckpt).startswith('synthetic') or os.environ.get('CSM_SYNTHETIC_WEIGHTS', '0') == '1'
+            self._animeseg_ws = load_animeseg_weights(refinenet_ckpt, synthetic)
         if refine_method == 'refinenet_isnet' and self._refine_ws is None:
             refinenet_ckpt = refinenet_ckpt or 'models/AnimeInstanceSegmentation/refine_last.ckpt'   # utils/constants.py:80
             synthetic = str(self.ckpt).startswith('synthetic') or os.environ.get('CSM_SYNTHETIC_WEIGHTS', '0') == '1'
@@ -156,6 +194,13 @@ class AnimeInsSeg:
             self._refine_programs[(n, T)] = cp
         return self._refine_programs[(n, T)]
 
+    def _animeseg_net(self, n, s):
+        """ISNet-IS (ISNetDIS(in_ch=3)) program for a batch of n letterboxed s x s frames"""
+        if (n, s) not in self._animeseg_programs:
+            prog = build_isnet(self._animeseg_ws, n, s, s, in_ch=3)
+            self._animeseg_programs[(n, s)] = CompiledProgram(prog, self.device, shared=self._animeseg_weights)
+        return self._animeseg_programs[(n, s)]
+
     # ---- public entry (reference :401-445) --------------------------------------------------------
     def infer(self, imgs, pred_score_thr: float = 0.3, refine_kwargs: dict = None, output_type: str = "tensor",
               det_size: int = None, save_dir: str = '', save_visualization: bool = False, save_annotation: str = '',
@@ -185,12 +230,16 @@ class AnimeInsSeg:
             insts = [self._instances_from(d, pred_score_thr) for d in self.detect_raw_batch(imgs)]
             if self.refine_method == 'refinenet_isnet':
                 self._refine_many(list(zip(insts, imgs)), self.refine_size)
+            elif self.refine_method == 'animeseg':
+                self._animeseg_refine(list(zip(insts, imgs)), self.refine_size)
         else:
             insts = []
             for img in imgs:
                 inst = self._det_forward(img, pred_score_thr)
                 if self.refine_method == 'refinenet_isnet':
                     self._postprocess_refine(inst, img, refine_size=self.refine_size)
+                elif self.refine_method == 'animeseg':
+                    self._animeseg_refine([(inst, img)], self.refine_size)
                 insts.append(inst)
         if output_type == 'numpy':
             for inst in insts:
@@ -468,3 +517,49 @@ class AnimeInsSeg:
                                          f32(self.mask_thr), ptr(out[k0:k0 + b]), stream_ptr()), "refine_threshold")
         masks = out.bool()
         instances.masks = masks.cpu().numpy() if was_numpy else masks
+
+    # ---- anime-seg refine (reference :78-115, :623-630; get_mask: animeseg_refine/__init__.py:169-188) ---------------------------
+    def _animeseg_fg(self, imgs_d, s, bgr_to_rgb=True, thr=0.5, prob=False):
+        """foreground of equally sized frames (u8 HWC on the device): one ISNet-IS batch of the letterboxed frames, then
+        sigmoid -> crop -> resize back -> (> thr) per frame.  Returns u8 [n,H0,W0] (or the fp32 probabilities with prob=True)."""
+        L = _lib.load()
+        H0, W0 = int(imgs_d[0].shape[0]), int(imgs_d[0].shape[1])
+        h, w = animeseg_size(H0, W0, s)
+        n = len(imgs_d)
+        out = torch.empty((n, H0, W0), dtype=torch.float32 if prob else torch.uint8, device=self.device)
+        for c0 in range(0, n, self.refine_batch):
+            chunk = imgs_d[c0:c0 + self.refine_batch]
+            b = len(chunk)
+            x = torch.empty((b, 3, s, s), dtype=torch.float32, device=self.device)
+            for i, img_d in enumerate(chunk):
+                check(L.csm_animeseg_prepare(ptr(img_d), i32(H0), i32(W0), i32(h), i32(w), i32(s), i32(1 if bgr_to_rgb else 0),
+                                             ptr(x[i]), stream_ptr()), "animeseg_prepare")
+            logits = torch.empty((b, 1, s, s), dtype=torch.float32, device=self.device)
+            self._animeseg_net(b, s).run(x, logits)
+            for i in range(b):
+                o = out[c0 + i]
+                check(L.csm_animeseg_mask(ptr(logits[i]), i32(s), i32(h), i32(w), i32(H0), i32(W0), f32(thr), ptr(o if prob else None),
+                                          ptr(None if prob else o), stream_ptr()), "animeseg_mask")
+        return out
+
+    def _animeseg_refine(self, pairs, refine_size=720):
+        """animeseg_refine for (instances, BGR image) pairs of equal image size, in place.  Frames without instances do not run the
+        net (reference :81-83).  Masks stay in their container: a bool tensor on its device, or bool numpy."""
+        L = _lib.load()
+        jobs = [(inst, self._upload(img)) for inst, img in pairs if not inst.is_empty]
+        if not jobs:
+            return
+        fg = self._animeseg_fg([img_d for _, img_d in jobs], refine_size)
+        W0 = int(fg.shape[2])
+        for (inst, _), f in zip(jobs, fg):
+            was_numpy = inst.is_numpy
+            src = torch.from_numpy(inst.masks) if was_numpy else inst.masks
+            masks = src.to(self.device).to(torch.uint8).contiguous()
+            k, Hm, Wm = (int(v) for v in masks.shape)
+            if Hm > f.shape[0] or Wm > W0:
+                raise _lib.CsmError("animeseg refine: %dx%d masks exceed the %dx%d frame" % (Hm, Wm, f.shape[0], W0))
+            counts = torch.empty(2 * k, dtype=torch.int32, device=self.device)
+            check(L.csm_animeseg_select(ptr(masks), i32(k), i32(Hm), i32(Wm), ptr(f), i32(W0), ptr(counts), stream_ptr()),
+                  "animeseg_select")
+            refined = masks.bool()
+            inst.masks = refined.cpu().numpy() if was_numpy else refined.to(src.device)

@@ -438,6 +438,25 @@ int csm_refine_prepare_batch(const uint8_t *img_hwc, const uint8_t *masks, int n
 int csm_refine_threshold(const float *logits, int n, int S_h, int S_w, int crop_h, int crop_w, int oh, int ow, float thr,
                          uint8_t *masks, void *stream);
 
+/* refine_method='animeseg' (animeinsseg/__init__.py:78-115, :623-630) around ISNetDIS(in_ch=3) (anime-seg ISNet-IS).
+ * get_mask input   animeinsseg/models/animeseg_refine/__init__.py:169-178: img u8 HWC [H,W,3] -> cv2 INTER_LINEAR u8 to (h,w)
+ * -> /255 into the zero s x s canvas at (ph/2, pw/2), ph = s-h, pw = s-w -> out fp32 NCHW [3,s,s] (one slot of a batch).  (h,w)
+ * is the host's letterbox rule (long side s, short side int(s * short / long)).  bgr_to_rgb = 1 swaps channels 0 and 2 (the
+ * cvtColor of animeseg_refine, :87-88); get_mask's own input is already RGB (0). */
+int csm_animeseg_prepare(const uint8_t *img_hwc, int H, int W, int h, int w, int s, int bgr_to_rgb, float *out_nchw, void *stream);
+
+/* get_mask tail   :180-188 (+ the threshold of animeseg_refine, :89-91): logits = d1 [s,s] of the net; sigmoid -> crop
+ * [ph/2:ph/2+h, pw/2:pw/2+w] -> cv2 float INTER_LINEAR to (H0,W0) -> prob_out fp32 [H0,W0], fg_out u8 [H0,W0] = prob > thr.
+ * Either output may be NULL. */
+int csm_animeseg_mask(const float *logits, int s, int h, int w, int H0, int W0, float thr, float *prob_out, uint8_t *fg_out,
+                      void *stream);
+
+/* animeseg_refine select   :96-105, in place: masks u8 [k,Hm,Wm] (0/1), fg u8 [>=Hm, W0] (row pitch W0, Wm <= W0).  Instance i
+ * becomes mask & fg[:Hm,:Wm] iff sum(mask & fg) / sum(mask) > 0.3 (float64 in the reference; decided exactly in integers), else
+ * stays.  counts_scratch: 2k uint32 of device memory.  Two launches, no host sync. */
+int csm_animeseg_select(uint8_t *masks_u8, int k, int Hm, int Wm, const uint8_t *fg, int W0, unsigned *counts_scratch,
+                        void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */
