@@ -534,3 +534,36 @@ def bokeh_blur(img, depth, num_samples=32, lightness_factor=10, depth_factor=2, 
     check(L.csm_bokeh_pass_finish(ptr(b), ptr(dm), ptr(out), i32(H), i32(W), i32(num_samples), f32(_math.cos(-PI * 5 / 6)),
                                   f32(_math.sin(-PI * 5 / 6)), f32(lightness_factor), stream_ptr()), "bokeh_pass_finish")
     return out
+
+
+def mask_rle_encode(masks):
+    """COCO compressed RLE of bool / uint8 device masks [n,H,W] (or one [H,W]): the 'counts' strings of
+    pycocotools.mask.encode (utils/io_utils.py:327-333 mask2rle; any non-zero byte is set) and the pixel counts.  Returns
+    (counts: list of str, areas: int64 numpy [n]).  The strings are built on the device (csm_mask_rle_measure / _write); the
+    host reads the small info array once, then only the characters."""
+    if not (isinstance(masks, torch.Tensor) and masks.is_cuda):
+        raise _lib.CsmError("mask_rle_encode: masks must be a device tensor; libcsm355 has no CPU path")
+    if masks.dtype not in (torch.bool, torch.uint8) or masks.dim() not in (2, 3):
+        raise _lib.CsmError("mask_rle_encode: bool or uint8 masks [n,H,W] or [H,W] expected (got %s %s)" % (masks.dtype, tuple(masks.shape)))
+    L = _lib.load()
+    m = masks.contiguous()                                  # named: alive until the kernels that read it are enqueued
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    n, H, W = (int(v) for v in m.shape)
+    if n == 0:
+        return [], _np.zeros(0, _np.int64)
+    if H * W > 2 ** 31 - 1:
+        raise _lib.CsmError("mask_rle_encode: H*W must stay below 2^31 (got %dx%d)" % (H, W))
+    dev = m.device
+    info = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    scratch = torch.empty(L.csm_mask_rle_scratch_bytes(i32(n), i32(H), i32(W)), dtype=torch.uint8, device=dev)
+    st = stream_ptr(dev)
+    check(L.csm_mask_rle_measure(ptr(m), i32(n), i32(H), i32(W), ptr(info), ptr(scratch), st), "mask_rle_measure")
+    info_h = info.cpu().numpy()                             # the one sync before the strings are sized
+    total = int(info_h[-1, 3] + info_h[-1, 1])
+    chars = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    check(L.csm_mask_rle_write(ptr(m), i32(n), i32(H), i32(W), ptr(info), ptr(chars), ptr(scratch), st), "mask_rle_write")
+    blob = chars[:total].cpu().numpy().tobytes()
+    counts = [blob[o:o + b].decode('ascii') for o, b in zip(info_h[:, 3].tolist(), info_h[:, 1].tolist())]
+    return counts, info_h[:, 2].copy()

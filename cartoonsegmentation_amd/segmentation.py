@@ -14,6 +14,7 @@ StateDictWeights; `ckpt="synthetic"` uses closed-form weights (no checkpoint exi
 mmdet's pieces are restated from mmdet 3.3.0 (not vendored in the reference => parity unpinned).
 """
 import ctypes
+import json
 import math
 import os
 from typing import List, Union
@@ -124,6 +125,25 @@ def config_from_ckpt_cfg(cfg_text):
     return c
 
 
+def coco_image_paths(json_path, val_dir=None):
+    """the part of pycocotools.COCO that _infer_save_annotations uses (reference :523-537): getImgIds() = the ids of `images` in
+    first-insertion order (a later entry with the same id replaces the earlier one), loadImgs(id)[0]['file_name'].  Returns the
+    image paths under val_dir (default: dirname(dirname(json_path))/val) and {path: image id}."""
+    with open(json_path, 'r') as f:
+        dataset = json.load(f)
+    metas = {}
+    for im in dataset.get('images', []):
+        metas[im['id']] = im
+    if val_dir is None:
+        val_dir = os.path.join(os.path.dirname(os.path.dirname(json_path)), 'val')
+    paths, ids = [], {}
+    for iid, meta in metas.items():
+        p = os.path.join(val_dir, meta['file_name'])
+        ids[p] = iid
+        paths.append(p)
+    return paths, ids
+
+
 class AnimeInsSeg:
     def __init__(self, ckpt: str, default_det_size: int = 640, device: str = None,
                  refine_kwargs: dict = {'refine_method': 'refinenet_isnet'},
@@ -211,17 +231,30 @@ class AnimeInsSeg:
         if refine_kwargs is not None:
             self.set_refine_method(**refine_kwargs)
         self.set_max_instance(max_instances)
-        if save_annotation or save_visualization or infer_tags:
-            raise NotImplementedError("annotation export / tagging are outside the hot-path scope (SURVEY 2.1)")
+        if save_visualization or infer_tags:
+            raise NotImplementedError("visualization / tagging are outside the hot-path scope (SURVEY 2.1)")
+        if isinstance(imgs, str) and imgs.endswith('.txt'):         # reference :437-439: a list of image paths
+            from utils.io_utils import read_imglst_from_txt
+            imgs = read_imglst_from_txt(imgs)
+        if save_annotation:                                         # reference :441-443 (save_mask_only is not forwarded there)
+            return self._infer_save_annotations(imgs, pred_score_thr, save_dir, save_annotation, obj_id_start, img_id_start, val_dir)
         assert output_type in {'tensor', 'numpy'}
         return_list = isinstance(imgs, list)
         if isinstance(imgs, str):                                 # prepare_data_pipeline, reference :667-693: a directory or one file
             if os.path.isdir(imgs):
                 from utils.io_utils import find_all_imgs
                 imgs, return_list = find_all_imgs(imgs, abs_path=True), True
-            elif imgs.endswith('.txt') or imgs.endswith('.json'):
-                raise NotImplementedError("image lists / COCO files belong to the annotation tooling (SURVEY 2.1)")
+            elif imgs.endswith('.json'):
+                raise NotImplementedError("COCO files are read by the annotation export only (infer(..., save_annotation=path))")
         imgs = imgs if return_list else [imgs]
+        insts = self._infer_frames(imgs, pred_score_thr)
+        if output_type == 'numpy':
+            for inst in insts:
+                inst.to_numpy()
+        return insts if return_list else insts[0]
+
+    def _infer_frames(self, imgs, pred_score_thr):
+        """detector + refine of a list of images (paths or BGR arrays) -> AnimeInstances with device masks"""
         if any(isinstance(im, str) for im in imgs):               # single_image_preprocess, reference :62-64: mmcv.imread(path)
             from utils.io_utils import imread
             imgs = [imread(im) if isinstance(im, str) else im for im in imgs]
@@ -241,10 +274,60 @@ class AnimeInsSeg:
                 elif self.refine_method == 'animeseg':
                     self._animeseg_refine([(inst, img)], self.refine_size)
                 insts.append(inst)
-        if output_type == 'numpy':
-            for inst in insts:
-                inst.to_numpy()
-        return insts if return_list else insts[0]
+        return insts
+
+    # ---- COCO annotation export (reference :506-621, :667-693) -------------------------------------------
+    def _infer_save_annotations(self, imgs, pred_score_thr, save_dir, save_annotation, obj_id_start, img_id_start, val_dir):
+        """infer every image and write the COCO instance-segmentation file `save_annotation`; returns None.  Frames run in chunks of
+        det_batch (the batched detector / refine when a chunk's frames are equally sized); each chunk's masks are RLE-encoded on the
+        device (ops.mask_rle_encode) and released before the next chunk, and no mask is copied to the host."""
+        from utils.constants import CATEGORIES
+        from utils.io_utils import dict2json, find_all_imgs, imread
+        from . import ops
+        imgp2ids = None
+        if isinstance(imgs, str) and imgs.endswith('.json'):
+            imgs, imgp2ids = coco_image_paths(imgs, val_dir)
+        target_dir = './workspace/output'
+        if isinstance(imgs, str):
+            if os.path.isdir(imgs):
+                target_dir, imgs = imgs, find_all_imgs(imgs, abs_path=True)
+            elif os.path.isfile(imgs):
+                target_dir, imgs = os.path.dirname(imgs), [imgs]
+            else:
+                raise FileNotFoundError(imgs)
+        elif not isinstance(imgs, list):
+            imgs = [imgs]
+        if save_dir == '':
+            save_dir = os.path.join(target_dir, os.path.basename(str(self.ckpt)).replace('.ckpt', '').replace('.pth', '').replace('.pt', ''))
+        os.makedirs(save_dir, exist_ok=True)
+        image_meta, det_annotations = [], []
+        obj_id, image_id = obj_id_start + 1, img_id_start + 1
+        for c0 in range(0, len(imgs), self.det_batch):
+            chunk = imgs[c0:c0 + self.det_batch]
+            frames = [imread(im) if isinstance(im, str) else im for im in chunk]
+            insts = self._infer_frames(frames, pred_score_thr)
+            for k, (src, frame, inst) in enumerate(zip(chunk, frames, insts)):
+                img_name = os.path.basename(src) if isinstance(src, str) else f'{c0 + k}'.zfill(12) + '.jpg'
+                if imgp2ids is not None:
+                    image_id = imgp2ids[src]
+                im_h, im_w = (int(v) for v in frame.shape[:2])
+                image_meta.append({"id": image_id, "height": im_h, "width": im_w, "file_name": img_name})
+                if not inst.is_empty:
+                    counts, areas = ops.mask_rle_encode(inst.masks)
+                    size = [int(inst.masks.shape[1]), int(inst.masks.shape[2])]         # the mask's shape, as the reference encodes it
+                    scores = inst.scores.tolist()
+                    bboxes = inst.bboxes.cpu().numpy().astype(np.float32).tolist()
+                    for j in range(len(inst)):
+                        det_annotations.append({'id': obj_id, 'category_id': 0, 'iscrowd': 0, 'score': float(scores[j]),
+                                                'segmentation': {'size': size, 'counts': counts[j]}, 'image_id': image_id,
+                                                'area': int(areas[j]), 'tag_string': inst.tags[j],
+                                                'tag_string_character': inst.character_tags[j], 'bbox': bboxes[j]})
+                        obj_id += 1
+                image_id += 1
+            del insts, frames
+        dict2json({"info": {}, "licenses": [], "images": image_meta, "annotations": det_annotations, "categories": CATEGORIES},
+                  save_annotation)
+        return None
 
     # ---- detector forward + post-process (reference :447-462 + mmdet predict_by_feat) ---------------
     def _upload(self, img):

@@ -457,6 +457,20 @@ int csm_animeseg_mask(const float *logits, int s, int h, int w, int H0, int W0, 
 int csm_animeseg_select(uint8_t *masks_u8, int k, int Hm, int Wm, const uint8_t *fg, int W0, unsigned *counts_scratch,
                         void *stream);
 
+/* COCO compressed RLE of n masks (maskrle.hip): the 'counts' string of utils/io_utils.py:327-333 mask2rle, i.e.
+ * pycocotools.mask.encode(np.asfortranarray(m[..., None] > 0).astype(np.uint8))[0]['counts'] (maskApi.c rleEncode + rleToString:
+ * column-major runs starting with the value 0, stored as differences to the count two before from the fourth count on).
+ * masks u8 [n,H,W] row-major, contiguous; any non-zero byte is set.  H*W <= 2^31-1, n <= 65535.
+ * scratch: csm_mask_rle_scratch_bytes(n, H, W) device bytes, O(n*W) (at most n*W*224), shared by the two calls.
+ * csm_mask_rle_measure: info device int64 [n][4] = {num_counts, string_bytes, area (pixels set), byte_offset}, byte_offset the
+ *   exclusive prefix of string_bytes (total bytes = info[n-1][3] + info[n-1][1]); leaves per-column carries in scratch.
+ * csm_mask_rle_write: instance i's string (no terminator) at out + info[i][3], for the same masks and scratch as the measure call
+ *   (a unit never writes outside its measured bytes).
+ * Five launches + one, async on the stream, no allocation, no sync, no atomics: the output is deterministic. */
+size_t csm_mask_rle_scratch_bytes(int n, int H, int W);
+int csm_mask_rle_measure(const uint8_t *masks, int n, int H, int W, int64_t *info, void *scratch, void *stream);
+int csm_mask_rle_write(const uint8_t *masks, int n, int H, int W, const int64_t *info, char *out, void *scratch, void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */

@@ -1,6 +1,9 @@
 """reference utils/io_utils.py -- the image helpers on the hot path's edge: find_all_imgs (:92-103), scaledown_maxsize
 (:254-274), resize_pad (:277-292), plus imread (mmcv.imread stand-in: the reference's callers decode with mmcv / cv2, which this
-image does not have).  The resamplers run on the MI355X (cv2's uint8 INTER_LINEAR arithmetic restated in imageops.hip)."""
+image does not have).  The resamplers run on the MI355X (cv2's uint8 INTER_LINEAR arithmetic restated in imageops.hip).
+The annotation helpers: NumpyEncoder / json2dict / dict2json (:24-47), mask2rle (:327-333; the RLE is built on the MI355X,
+csrc/maskrle.hip) and read_imglst_from_txt (animeinsseg/__init__.py:179-183)."""
+import json
 import os
 import os.path as osp
 from pathlib import Path
@@ -85,3 +88,49 @@ def resize_pad(img, tgt_size: int, pad_value=(0, 0, 0)):
             else:
                 img = np.pad(img, pads, mode='constant', constant_values=v)
     return img, (0, pb, 0, pr)
+
+
+class NumpyEncoder(json.JSONEncoder):
+    """utils/io_utils.py:24-35: numpy arrays -> lists, numpy scalars -> bool / float / int"""
+    def default(self, obj):
+        if isinstance(obj, np.ndarray):
+            return obj.tolist()
+        if isinstance(obj, np.bool_):
+            return bool(obj)
+        if isinstance(obj, np.floating):
+            return float(obj)
+        if isinstance(obj, np.integer):
+            return int(obj)
+        return json.JSONEncoder.default(self, obj)
+
+
+def json2dict(json_path: str):
+    with open(json_path, 'r', encoding='utf8') as f:
+        return json.loads(f.read())
+
+
+def dict2json(adict: dict, json_path: str):
+    with open(json_path, "w", encoding="utf-8") as f:
+        f.write(json.dumps(adict, ensure_ascii=False, cls=NumpyEncoder))
+
+
+def read_imglst_from_txt(filep):
+    """animeinsseg/__init__.py:179-183: one image path per line"""
+    with open(filep, 'r', encoding='utf8') as f:
+        return f.read().splitlines()
+
+
+def mask2rle(mask, decode_for_json: bool = True):
+    """utils/io_utils.py:327-333: {'size': [h, w], 'counts': COCO compressed RLE of mask > 0} (str, or bytes with
+    decode_for_json=False).  mask: an [h, w] numpy array (uploaded) or device tensor; the string is built on the MI355X."""
+    import torch
+    from cartoonsegmentation_amd import ops
+    if isinstance(mask, torch.Tensor):
+        m = mask if mask.dtype in (torch.bool, torch.uint8) else mask > 0
+    else:
+        a = np.asarray(mask)
+        m = torch.from_numpy(np.ascontiguousarray(a if a.dtype in (np.bool_, np.uint8) else a > 0)).cuda()
+    if m.dim() != 2:
+        raise ValueError("mask2rle: an [h, w] mask is expected (got shape %s)" % (tuple(m.shape),))
+    counts, _ = ops.mask_rle_encode(m)
+    return {'size': [int(m.shape[0]), int(m.shape[1])], 'counts': counts[0] if decode_for_json else counts[0].encode()}
