@@ -361,9 +361,10 @@ class KenBurnsPipeline:
         return ops.denormalise(out, ms_d, 2)                                  # * (std + 1e-7) + mean, threshold(0)
 
     def set_inpainting(self, inpainting: str):
-        """kenburns_effect.py:425-440: 'default' = the Inpaint GridNet; 'ldm'/'patchmatch' call external services"""
-        if inpainting != 'default':
-            raise NotImplementedError("inpaint_type %r needs stable-diffusion-webui / libpatchmatch (out of scope, SURVEY 2.1)" % inpainting)
+        """kenburns_effect.py:425-440: 'default' = the Inpaint GridNet; 'patchmatch' = the GridNet, then PatchMatch over its image
+        (csrc/patchmatch.hip); 'ldm' calls an external stable-diffusion service (out of scope)"""
+        if inpainting not in ('default', 'patchmatch'):
+            raise NotImplementedError("inpaint_type %r needs stable-diffusion-webui (out of scope, SURVEY 2.1)" % inpainting)
         self.inpaint_type = inpainting
         if getattr(self, '_inpaint_ws', None) is None:
             p = 'models/AnimeInstanceSegmentation/kenburns_inpaintnet.ckpt'          # utils/constants.py:82
@@ -425,8 +426,9 @@ class KenBurnsPipeline:
                 'tenDisparity': ops.denormalise(dsp, ms_d, 2), 'segmasks': segmasks}       # ..., threshold(0)
 
     def inpaint(self, tenShift, tenPoints, objCommon: KenBurnsConfig, verbose: bool = False):
-        """kenburns_effect.py:441-512 (inpaint_type 'default'): inpaint the view at `tenShift` and append the points that
-        fill its holes to the cloud (N grows, data dependent)."""
+        """kenburns_effect.py:441-512: inpaint the view at `tenShift` and append the points that fill its holes to the cloud (N grows,
+        data dependent).  inpaint_type 'patchmatch' (:497-503) replaces the GridNet's colours by PatchMatch over its u8 image with
+        the holes and the rendered instance masks as the hole mask; disparity, depth and points stay the GridNet's."""
         ins = objCommon.instances
         mask_with_ins = None
         if ins is not None and not ins.is_empty:
@@ -440,6 +442,8 @@ class KenBurnsPipeline:
         pts = pts.view(1, 3, -1) - tenShift
         tenMask = (o['tenExisting'] == 0.0).view(1, 1, -1)
         m1, m3 = tenMask[0, 0], tenMask.repeat(1, 3, 1)
+        if self.inpaint_type == 'patchmatch':
+            o['tenImage'] = self._patchmatch_image(o)
         objCommon.inpainted_img = torch.cat([objCommon.inpainted_img, o['tenImage'].view(1, 3, -1)[m3].view(1, 3, -1)], 2)
         objCommon['tenInpaDisparity'] = torch.cat([objCommon['tenInpaDisparity'], o['tenDisparity'].view(1, 1, -1)[:, :, m1]], 2)
         objCommon['tenInpaDepth'] = torch.cat([objCommon['tenInpaDepth'], depth_t.view(1, 1, -1)[:, :, m1]], 2)
@@ -450,6 +454,16 @@ class KenBurnsPipeline:
             objCommon.stage_inpainted_imgs.append((o['tenImage'][0] * 255).to(torch.uint8).permute(1, 2, 0).cpu().numpy())
             objCommon.stage_inpainted_masks.append((tenMask.view(objCommon.int_height, objCommon.int_width).to(torch.uint8) * 255).cpu().numpy())
         return o
+
+    def _patchmatch_image(self, o):
+        """kenburns_effect.py:484-488, :497-503 on the device: (x * 255).astype(uint8) of the GridNet image, hole mask
+        (tenExisting == 0) | (segmasks[0, 0] > 0), patch_match.inpaint(..., patch_size=3), back as u8 * float32(1 / 255)"""
+        hole = o['tenExisting'][0, 0] == 0.0
+        if o['segmasks'] is not None:
+            hole = hole | (o['segmasks'][0, 0] > 0)
+        u8 = (o['tenImage'][0] * 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+        pm = ops.patchmatch_inpaint(u8, hole.to(torch.uint8), patch_size=3)
+        return (pm.permute(2, 0, 1).unsqueeze(0).to(torch.float32) * float(np.float32(1.0 / 255.0))).contiguous()
 
     # ---- depth (kenburns_effect.py:563-581) ------------------------------------------------------------
     def _leres_prog(self, h, w, n=1, slot=0):

@@ -567,3 +567,49 @@ def mask_rle_encode(masks):
     blob = chars[:total].cpu().numpy().tobytes()
     counts = [blob[o:o + b].decode('ascii') for o, b in zip(info_h[:, 3].tolist(), info_h[:, 1].tolist())]
     return counts, info_h[:, 2].copy()
+
+
+# ---- PatchMatch inpainting (animeinsseg/inpainting/patch_match.py; kenburns_effect.py:497-503) ----------------------------
+def patchmatch_inpaint(img, mask, global_mask=None, patch_size=15, seed=0):
+    """PatchMatch inpainting of device uint8 [H,W,3] `img` where the device uint8 `mask` ([H,W] or [H,W,1]) is non-zero;
+    `global_mask` (same shapes) marks pixels that never serve inside a source patch.  Returns a new device uint8 [H,W,3]: known
+    pixels unchanged, holes filled by the coarse-to-fine EM of csrc/patchmatch.hip (contract DESIGN.md §4.5, deterministic for a
+    given seed).  The host reads the per-level counts once, between csm_patchmatch_prepare and csm_patchmatch_run."""
+    for name, t in (("img", img), ("mask", mask), ("global_mask", global_mask)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise _lib.CsmError("patchmatch_inpaint: %s must be a device tensor; libcsm355 has no CPU path" % name)
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise _lib.CsmError("patchmatch_inpaint: img must be uint8 [H,W,3] (got %s %s)" % (img.dtype, tuple(img.shape)))
+    H, W = int(img.shape[0]), int(img.shape[1])
+    p = int(patch_size)
+    if p < 3 or p > 15 or p % 2 == 0:
+        raise ValueError("patchmatch_inpaint: patch_size must be odd and in [3, 15] (got %d)" % p)
+    if H < p or W < p:
+        raise ValueError("patchmatch_inpaint: image %dx%d is smaller than the patch size %d" % (H, W, p))
+
+    def flat(m, name):
+        if m is None:
+            return None
+        if m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) not in ((H, W), (H, W, 1)):
+            raise _lib.CsmError("patchmatch_inpaint: %s must be uint8 [H,W] or [H,W,1] (got %s %s)" % (name, m.dtype, tuple(m.shape)))
+        m = m.contiguous()
+        return m.view(torch.uint8) if m.dtype == torch.bool else m
+    import ctypes
+    L = _lib.load()
+    im, mk, gm = img.contiguous(), flat(mask, "mask"), flat(global_mask, "global_mask")   # named: alive until the kernels are enqueued
+    dev = im.device
+    n = L.csm_patchmatch_levels(i32(H), i32(W), i32(p))
+    info = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    scratch = torch.empty(L.csm_patchmatch_scratch_bytes(i32(H), i32(W), i32(p)), dtype=torch.uint8, device=dev)
+    st = stream_ptr(dev)
+    check(L.csm_patchmatch_prepare(ptr(im), ptr(mk), ptr(gm), i32(H), i32(W), i32(p), ptr(info), ptr(scratch), st), "patchmatch_prepare")
+    info_h = _np.ascontiguousarray(info.cpu().numpy())     # the one sync: the schedule
+    if info_h[0, 0] == 0 or info_h[0, 1] == 0:             # no valid source, or nothing to fill
+        return im.clone()
+    levels = 1
+    while levels < n and info_h[levels, 0] > 0:
+        levels += 1
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    check(L.csm_patchmatch_run(i32(H), i32(W), i32(p), i32(levels), info_h.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                               ctypes.c_uint(int(seed) & 0xFFFFFFFF), ptr(out), ptr(scratch), st), "patchmatch_run")
+    return out

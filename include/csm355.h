@@ -471,6 +471,25 @@ size_t csm_mask_rle_scratch_bytes(int n, int H, int W);
 int csm_mask_rle_measure(const uint8_t *masks, int n, int H, int W, int64_t *info, void *scratch, void *stream);
 int csm_mask_rle_write(const uint8_t *masks, int n, int H, int W, const int64_t *info, char *out, void *scratch, void *stream);
 
+/* PatchMatch inpainting (patchmatch.hip; contract DESIGN.md §4.5, restated in tests/patchmatch_restatement.py, byte-identical):
+ * the patch_match.inpaint(img, mask, patch_size) of kenburns_effect.py:497-503, repaint_person.py:122, run_style.py:182.
+ * img u8 [H,W,3], mask u8 [H,W] (non-zero = hole), global_mask u8 [H,W] or NULL (non-zero = never inside a source patch);
+ * p odd in [3, 15], H, W >= p, H*W <= 2^28.
+ * csm_patchmatch_levels: the pyramid levels prepare builds (0 for an invalid shape).
+ * csm_patchmatch_scratch_bytes: device scratch shared by the two calls (about 30 B per pixel of the pyramid).
+ * csm_patchmatch_prepare: pyramid, roles and ordered lists; info device int32 [levels][4] = {valid sources, targets, hole pixels,
+ *   known pixels} per level.  The caller reads info once and schedules the run: the levels used are level 0 and the following
+ *   levels while each still has a valid source; with no valid source (or no target) at level 0 the result is the input.
+ * csm_patchmatch_run: the EM completion over `levels` levels with info_host = that host copy of info; writes out u8 [H,W,3]
+ *   (known pixels unchanged).  The random draws are a counter hash of (seed, level, iteration, pass, pixel, sample).
+ * Async on the stream, no allocation, no sync; a few hundred launches at 1024^2. */
+int csm_patchmatch_levels(int H, int W, int p);
+size_t csm_patchmatch_scratch_bytes(int H, int W, int p);
+int csm_patchmatch_prepare(const uint8_t *img, const uint8_t *mask, const uint8_t *global_mask, int H, int W, int p, int *info,
+                           void *scratch, void *stream);
+int csm_patchmatch_run(int H, int W, int p, int levels, const int *info_host, unsigned seed, uint8_t *out, void *scratch,
+                       void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */
