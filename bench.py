@@ -3,12 +3,15 @@
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR               (also writes the last timed step's outputs as DIR/<name>.npy)
+    python bench.py ... --full                           (also everything that is not the headline: see below)
 
 A "step" is one pass of the hot path over `--batch` (default 8) 1024x1024 frames per rank (weak
 scaling: every rank owns its own frames, 8 per rank = BASELINE configs[3]'s 64 frames on 8 GPUs;
 SURVEY.md 8e; outputs are gathered to rank 0 over RCCL inside the timed region).  Inputs are synthetic, seeded and already resident in HBM when timing starts.
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed on the launch stream) and `cpu_baseline` (the oracle timed on this host).
+Rank 0 prints ONE JSON line.  A plain run sets up (the first, untimed step builds and tunes the programs), warms up, times the
+steps and prints the headline (`value`, `ms_per_step`, `config`).  `--full` then adds, after the timed steps, `roofline`
+(dominant kernel, HIP-event timed on the launch stream), `cpu_baseline` (the oracle timed on this host), `mask_iou_vs_oracle`,
+the workload's extra figures and the single-GPU `variants`; the --no-* switches leave parts of a --full run out.
 """
 import argparse
 import json
@@ -35,11 +38,13 @@ def parse():
     ap.add_argument("--workload", default="auto", help="auto | warp | frame")
     ap.add_argument("--batch", type=int, default=8, help="frames per GPU per step (frame workload); 8 per rank = BASELINE configs[3] "
                                                         "(64 frames on 8 GPUs), and the same per-rank work at every N (weak scaling)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra single-GPU measurements (batch / instances / det size / video)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-iou", action="store_true", help="skip the one-frame mask IoU against the CPU oracle (about 20 s of host time, untimed)")
-    ap.add_argument("--no-roofline", action="store_true", help="profiling runs: skip the per-op HIP-event pass, so that the process executes "
-                                                               "exactly 1 + warmup + steps steps (rocprofv3 totals divide cleanly)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline does not need: "
+                                                        "roofline, CPU baseline, mask IoU vs the oracle, the workload's extra figures and "
+                                                        "the single-GPU variants (a plain run executes exactly 1 + warmup + steps steps)")
+    ap.add_argument("--no-variants", action="store_true", help="--full without the extra single-GPU measurements (batch / instances / det size / video)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-iou", action="store_true", help="--full without the one-frame mask IoU against the CPU oracle (about 20 s of host time)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the per-op HIP-event pass")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
                                                           "(float32 / float64, at most 64 MB; a seeded sample of pixels when the "
                                                           "full outputs would not fit) so that two builds can be compared output for output")
@@ -823,6 +828,26 @@ def dump_outputs(arrays, out_dir, seed=0):
     return {k: list(v.shape) for k, v in out.items()}
 
 
+def full_report(out, wl, a, world):
+    """--full: what the headline does not need, measured after its timed steps on rank 0 (each item reruns the workload or the oracle)"""
+    out["roofline"] = None if a.no_roofline else wl.roofline()
+    if world == 1 and not a.no_cpu_baseline:
+        out["cpu_baseline"] = wl.cpu_baseline(a.cpu_seconds)
+    if world == 1 and not a.no_iou and hasattr(wl, "mask_iou_vs_oracle"):
+        out["mask_iou_vs_oracle"] = wl.mask_iou_vs_oracle()    # BASELINE.json's `mask IoU vs ref`; the oracle is the checker, untimed
+    out.update(wl.extra())
+    if world == 1 and not a.no_variants and hasattr(wl, "variants"):
+        out["variants"] = wl.variants()
+        b1 = out["variants"].get("batch1")
+        if b1:             # the literal BASELINE configs[1..2] (one frame per step) next to the headline (configs[3]'s 8 frames per rank)
+            out["batch1"] = {"frames_per_s": b1["frames_per_s"], "ms_per_frame": b1["ms_per_frame"],
+                             "conv_frac_of_mfma_peak": b1.get("conv_frac_of_mfma_peak"),
+                             "frames_per_s_3_in_flight": out["variants"].get("batch1_lanes3", {}).get("frames_per_s"),
+                             "frames_per_s_4_in_flight": out["variants"].get("batch1_lanes4", {}).get("frames_per_s"),
+                             "what": "BASELINE configs[1..2] literally: ONE 1024x1024 frame per step (seg + depth + warp), serial loop; "
+                                     "*_in_flight: the same single-frame steps with 3 / 4 frames in flight (FrameLanes)"}
+
+
 def main():
     a = parse()
     if os.environ.get("CSM_BENCH_WATCHDOG"):          # debugging aid: dump every thread's stack and exit after N seconds
@@ -927,22 +952,8 @@ def main():
                "config": wl.config(world)}
         if dumped is not None:
             out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
-        out["roofline"] = None if a.no_roofline else wl.roofline()
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = wl.cpu_baseline(a.cpu_seconds)
-        if world == 1 and not a.no_iou and hasattr(wl, "mask_iou_vs_oracle"):
-            out["mask_iou_vs_oracle"] = wl.mask_iou_vs_oracle()    # BASELINE.json's `mask IoU vs ref`; the oracle is the checker, untimed
-        out.update(wl.extra())
-        if world == 1 and not a.no_variants and hasattr(wl, "variants"):
-            out["variants"] = wl.variants()
-            b1 = out["variants"].get("batch1")
-            if b1:             # the literal BASELINE configs[1..2] (one frame per step) next to the headline (configs[3]'s 8 frames per rank)
-                out["batch1"] = {"frames_per_s": b1["frames_per_s"], "ms_per_frame": b1["ms_per_frame"],
-                                 "conv_frac_of_mfma_peak": b1.get("conv_frac_of_mfma_peak"),
-                                 "frames_per_s_3_in_flight": out["variants"].get("batch1_lanes3", {}).get("frames_per_s"),
-                                 "frames_per_s_4_in_flight": out["variants"].get("batch1_lanes4", {}).get("frames_per_s"),
-                                 "what": "BASELINE configs[1..2] literally: ONE 1024x1024 frame per step (seg + depth + warp), serial loop; "
-                                         "*_in_flight: the same single-frame steps with 3 / 4 frames in flight (FrameLanes)"}
+        if a.full:
+            full_report(out, wl, a, world)
         if dist is not None:
             out["process_group"] = {"backend": dist.get_backend(), "world_size": world}
             out["gather"] = wl.check_gathered()

@@ -460,7 +460,7 @@ def test_bench_two_ranks_end_to_end(tmp_path):
                CSM_BENCH_WATCHDOG="500")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "2", "--size", "320", "--steps", "1",
-           "--warmup", "0"]
+           "--warmup", "0", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1]
@@ -496,6 +496,27 @@ def test_bench_process_group_path_on_rccl_with_one_rank():
     assert d["process_group"] == {"backend": "nccl", "world_size": 1} and d["n_gpus"] == 1
     assert d["weights_broadcast_bytes"] > 1e8 and d["weights_equal_after_broadcast"] is True
     assert d["gather"]["records_ok"] is True and d["value"] > 0
+
+
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps, --dump-outputs and the headline line -- none of the items that
+    rerun the workload or the oracle (roofline, CPU baseline, mask IoU, variants) is measured or reported"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CSM_SYNTHETIC_WEIGHTS="1", CSM_BENCH_WATCHDOG="500")
+    env.pop("CSM_BENCH_FORCE_DIST", None)
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "2", "--size", "320", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d)
+    assert d["value"] > 0 and d["steps"] == 2 and d["warmup"] == 1 and d["config"]["frames_per_gpu_step"] == 2
+    assert not {"roofline", "cpu_baseline", "mask_iou_vs_oracle", "variants", "batch1"} & set(d)
+    assert sorted(os.listdir(dump)) == sorted(k + ".npy" for k in d["dumped_outputs"]["arrays"])
 
 
 def test_default_depth_estimator_pipeline():

@@ -3,7 +3,7 @@
 O=gpurun_out/r05d; mkdir -p $O
 export CSM_SYNTHETIC_WEIGHTS=1
 LP_BATCH=8 timeout 900 python tools/layer_profile.py > $O/lp_b8.txt 2>&1; grep -v amdgpu.ids $O/lp_b8.txt
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; python - <<PY
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; python - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
 print({k: d[k] for k in ("value", "ms_per_step")}, {k: d["roofline"][k] for k in ("achieved", "frac", "direct_equivalent_tflops", "conv_ms_per_step", "winograd_ms_per_step", "winograd_launches_per_step")})

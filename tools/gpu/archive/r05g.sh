@@ -3,7 +3,7 @@
 O=gpurun_out/r05g; mkdir -p $O
 export CSM_SYNTHETIC_WEIGHTS=1
 timeout 900 python -m pytest tests/test_gpu_warp.py tests/test_gpu_dpt_beit.py tests/test_gpu_nets.py tests/test_gpu_kenburns.py -m gpu -q -x -k "multi_frame or bounded or percentiles or zoe or pointwise" > $O/pytest_sel.txt 2>&1; tail -12 $O/pytest_sel.txt
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; python - <<PY
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; python - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
 print({k: d[k] for k in ("value", "ms_per_step")}, {k: d["roofline"][k] for k in ("achieved", "frac", "direct_equivalent_tflops", "conv_ms_per_step", "winograd_ms_per_step")})

@@ -3,7 +3,7 @@
 R=$PWD; O=$R/gpurun_out/r06e; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_winograd4.py -x -q 2>&1 | tail -3
 for S in 500 6400; do
-  CSM_WINO4_SMALL_MIN_PIXELS=$S timeout 600 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_small$S.json
+  CSM_WINO4_SMALL_MIN_PIXELS=$S timeout 600 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_small$S.json
   python - <<PY
 import json
 d=json.load(open("$O/bench_small$S.json"))
