@@ -684,13 +684,15 @@ class KenBurnsPipeline:
         """common.py:86-142 through the batched coverage kernels (ops.process_autozoom)"""
         return ops.process_autozoom(objSettings, objCommon)
 
-    def autozoom(self, cfg: KenBurnsConfig, verbose: bool = False, inpaint: bool = True):
+    def autozoom(self, cfg: KenBurnsConfig, verbose: bool = False, inpaint: bool = True, to_numpy: bool = True):
+        """kenburns_effect.py:953-977; to_numpy=False returns the frames as one device tensor [n,H,W,3] (what npyframes2video's
+        .avi route takes without a copy to the host)"""
         with torch.no_grad():
             objFrom = {'fltCenterU': cfg.int_width / 2.0, 'fltCenterV': cfg.int_height / 2.0,
                        'intCropWidth': int(math.floor(0.97 * cfg.int_width)), 'intCropHeight': int(math.floor(0.97 * cfg.int_height))}
             objTo = self.process_autozoom({'fltShift': 100.0, 'fltZoom': 1.25, 'objFrom': objFrom}, cfg)
             frames, _ = self.process_kenburns({'fltSteps': np.linspace(0.0, 1.0, cfg.num_frame).tolist(), 'objFrom': objFrom,
-                                               'objTo': objTo, 'boolInpaint': True}, cfg, inpaint, verbose)
+                                               'objTo': objTo, 'boolInpaint': True}, cfg, inpaint, verbose, to_numpy=to_numpy)
             return frames
 
     def _focal_end(self, depth_u8, ins):
@@ -797,8 +799,25 @@ class KenBurnsPipeline:
             return [frames, objCommon]
 
 
-def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False):
-    """kenburns_effect.py:1086-1090 (BGR->RGB, optional ping-pong, 25 fps mp4 through moviepy)"""
+def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False, quality: int = 90, subsampling: str = '420'):
+    """kenburns_effect.py:1086-1090 (BGR->RGB, optional ping-pong, 25 fps mp4 through moviepy).
+
+    A path ending in .avi (any letter case) is written as a Motion-JPEG AVI instead: the frames -- a list of BGR numpy frames,
+    which is uploaded, or the device tensor [n,H,W,3] of process_kenburns(to_numpy=False) -- are JPEG-encoded on the device
+    (ops.jpeg_encode with `quality` and `subsampling`) and only the compressed bytes cross to the host.  With playback each frame
+    is still encoded once; the file holds the reference's seq + seq[::-1][1:-1], 2n - 2 chunks."""
+    if str(video_save_path).lower().endswith('.avi'):
+        from . import video
+        if isinstance(npy_frame_list, torch.Tensor):
+            frames = npy_frame_list
+        else:
+            frames = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in npy_frame_list]))).to('cuda')
+        if frames.dim() == 3:
+            frames = frames.unsqueeze(0)
+        jpegs = ops.jpeg_encode(frames, quality=quality, subsampling=subsampling)
+        order = video.playback_order(len(jpegs)) if playback else None
+        video.write_mjpeg_avi(video_save_path, jpegs, int(frames.shape[2]), int(frames.shape[1]), fps=25, order=order)
+        return
     sequence = [f[:, :, ::-1] for f in npy_frame_list]
     if playback:
         sequence += sequence[::-1][1:-1]

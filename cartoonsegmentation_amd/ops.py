@@ -569,6 +569,50 @@ def mask_rle_encode(masks):
     return counts, info_h[:, 2].copy()
 
 
+# ---- baseline JPEG of device frames (csrc/mjpeg.hip; the frames of video.write_mjpeg_avi) ---------------------------------
+JPEG_SCRATCH_BYTES = 64 << 20          # frames are encoded in chunks whose scratch stays below this (one frame is always taken)
+
+
+def jpeg_encode(frames, quality=90, subsampling='420'):
+    """Baseline JPEG (JFIF, Annex K tables, one restart interval per MCU row; contract DESIGN.md §4.6) of device uint8 frames
+    [n,H,W,3] (or one [H,W,3]) in B, G, R order.  Returns a list of n `bytes`, each a complete JPEG file.  quality 1..100 scales
+    the quantisation tables by the IJG rule; subsampling is '420' (the default) or '444'.  The streams are built on the device
+    (csm_jpeg_measure / _write) in chunks of frames whose scratch stays below JPEG_SCRATCH_BYTES; per chunk the host reads the
+    [k,2] size table once, then only the bytes."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, _np.integer)) or not 1 <= quality <= 100:
+        raise ValueError("jpeg_encode: quality must be an integer in [1, 100] (got %r)" % (quality,))
+    if subsampling not in ('420', '444'):
+        raise ValueError("jpeg_encode: subsampling must be '420' or '444' (got %r)" % (subsampling,))
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+        raise _lib.CsmError("jpeg_encode: frames must be a device tensor; libcsm355 has no CPU path")
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise _lib.CsmError("jpeg_encode: uint8 frames [n,H,W,3] or [H,W,3] expected (got %s %s)" % (frames.dtype, tuple(frames.shape)))
+    fr = frames.contiguous()                                # named: alive until the kernels that read it are enqueued
+    if fr.dim() == 3:
+        fr = fr.unsqueeze(0)
+    n, H, W = (int(v) for v in fr.shape[:3])
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError("jpeg_encode: H and W must be in [1, 65535] (got %dx%d)" % (H, W))
+    L, dev, st = _lib.load(), fr.device, stream_ptr(fr.device)
+    q, sub = i32(int(quality)), i32(int(subsampling))
+    per_frame = L.csm_jpeg_scratch_bytes(i32(1), i32(H), i32(W), sub)
+    step = max(1, JPEG_SCRATCH_BYTES // per_frame)
+    out = []
+    for f0 in range(0, n, step):
+        part = fr[f0:f0 + step]
+        k = int(part.shape[0])
+        info = torch.empty((k, 2), dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.csm_jpeg_scratch_bytes(i32(k), i32(H), i32(W), sub), dtype=torch.uint8, device=dev)
+        check(L.csm_jpeg_measure(ptr(part), i32(k), i32(H), i32(W), q, sub, ptr(info), ptr(scratch), st), "jpeg_measure")
+        info_h = info.cpu().numpy()                         # the one sync before the blob is sized
+        total = int(info_h[-1, 0] + info_h[-1, 1])
+        blob = torch.empty(total, dtype=torch.uint8, device=dev)
+        check(L.csm_jpeg_write(i32(k), i32(H), i32(W), q, sub, ptr(info), ptr(blob), ptr(scratch), st), "jpeg_write")
+        host = blob.cpu().numpy().tobytes()
+        out += [host[o:o + b] for o, b in info_h.tolist()]
+    return out
+
+
 # ---- PatchMatch inpainting (animeinsseg/inpainting/patch_match.py; kenburns_effect.py:497-503) ----------------------------
 def patchmatch_inpaint(img, mask, global_mask=None, patch_size=15, seed=0):
     """PatchMatch inpainting of device uint8 [H,W,3] `img` where the device uint8 `mask` ([H,W] or [H,W,1]) is non-zero;

@@ -490,6 +490,28 @@ int csm_patchmatch_prepare(const uint8_t *img, const uint8_t *mask, const uint8_
 int csm_patchmatch_run(int H, int W, int p, int levels, const int *info_host, unsigned seed, uint8_t *out, void *scratch,
                        void *stream);
 
+/* Baseline JPEG of n equally sized frames (mjpeg.hip; contract DESIGN.md §4.6, restated in tests/mjpeg_restatement.py,
+ * byte-identical): the frames of a Motion-JPEG AVI.  frames u8 [n,H,W,3] (B, G, R), contiguous; 1 <= H, W <= 65535;
+ * quality 1..100 (IJG scaling of the Annex K tables); subsampling 420 (16x16 MCU) or 444 (8x8 MCU).  Every frame is a complete
+ * JFIF file: SOI, APP0, two DQT, SOF0, four DHT (Annex K), DRI (= MCUs per row), SOS, one segment per MCU row with RSTm between
+ * them, EOI.
+ * scratch: csm_jpeg_scratch_bytes(n, H, W, subsampling) device bytes, shared by the two calls: int16 coefficients (3 B per padded
+ *   pixel at 4:2:0, 6 B at 4:4:4), 12 B per MCU row, and at most 32 MiB (or one row's worst case) for rows too wide for LDS
+ *   (more than 739 blocks: wider than 1968 pixels).  0 for an invalid shape.
+ * csm_jpeg_header_bytes: bytes of a frame before its entropy data (the same for every frame).
+ * csm_jpeg_measure: transform + bytes of every MCU row; info device int64 [n][2] = {offset, bytes} of each frame in the blob
+ *   (offset the exclusive prefix of bytes; total = info[n-1][0] + info[n-1][1]).
+ * csm_jpeg_write: frame f at out + info[f][0], for the same arguments and scratch as the measure call (a row never writes
+ *   outside its measured bytes).
+ * Four launches + one (more for the wide rows), async on the stream, no allocation, no sync; the only atomics are integer ORs of
+ * disjoint bits, so the output is deterministic. */
+size_t csm_jpeg_scratch_bytes(int n, int H, int W, int subsampling);
+int csm_jpeg_header_bytes(void);
+int csm_jpeg_measure(const uint8_t *frames, int n, int H, int W, int quality, int subsampling, int64_t *info, void *scratch,
+                     void *stream);
+int csm_jpeg_write(int n, int H, int W, int quality, int subsampling, const int64_t *info, uint8_t *out, void *scratch,
+                   void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */
