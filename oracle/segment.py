@@ -34,10 +34,12 @@ ci, cf = ctypes.c_int, ctypes.c_float
 
 
 def det_preprocess(img, S, cfg, rh, rw):
+    """S: the detector's square size, or (S_h, S_w)"""
     H, W = img.shape[:2]
-    x = np.empty((1, 3, S, S), np.float32)
+    S_h, S_w = (S, S) if np.isscalar(S) else S
+    x = np.empty((1, 3, S_h, S_w), np.float32)
     mean, std = np.asarray(cfg.mean, np.float32), np.asarray(cfg.std, np.float32)
-    lib().orc_det_preprocess(_p(np.ascontiguousarray(img)), ci(H), ci(W), ci(rh), ci(rw), ci(S), ci(S), _p(mean), _p(std),
+    lib().orc_det_preprocess(_p(np.ascontiguousarray(img)), ci(H), ci(W), ci(rh), ci(rw), ci(S_h), ci(S_w), _p(mean), _p(std),
                              cf(cfg.pad_value), _p(x))
     return x
 
@@ -49,11 +51,14 @@ def nms(boxes, offs, thr, max_keep):
     return keep[:n]
 
 
-def maskhead_logits(mask_feat_hwc, kernels, priors, feat_stride):
+def maskhead_logits(mask_feat_hwc, kernels, priors, feat_stride, c0=0):
+    """mask_feat_hwc [h, w, ld]: the 8 prototype channels are c0 .. c0+7 of a buffer of channel pitch ld"""
     h, w, c = mask_feat_hwc.shape
     n = len(priors)
     out = np.empty((n, h, w), np.float32)
-    lib().orc_maskhead_logits(_p(np.ascontiguousarray(mask_feat_hwc)), ci(c), ci(h), ci(w), _p(np.ascontiguousarray(kernels, np.float32)),
+    feat = np.ascontiguousarray(mask_feat_hwc, np.float32)
+    assert 0 <= c0 <= c - 8
+    lib().orc_maskhead_logits(ctypes.c_void_p(feat.ctypes.data + 4 * c0), ci(c), ci(h), ci(w), _p(np.ascontiguousarray(kernels, np.float32)),
                               _p(np.ascontiguousarray(priors, np.float32)), ci(n), ci(feat_stride), _p(out))
     return out
 

@@ -1,10 +1,16 @@
 """GPU parity of AnimeInsSeg.infer() (HIP path through the drop-in import surface) vs the CPU oracle pipeline:
 instance indices, boxes, scores and masks after threshold must be IDENTICAL (north_star: bit-exact masks)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from detpost_cases import decode_reference  # noqa: E402
 
 
 def _img(h, w, seed):
@@ -168,24 +174,9 @@ def test_device_decode_matches_filter_then_topk_with_ties_and_classes():
                            ptr(scratch), stream_ptr()))
     prior0 = [0, 120, 150]
     for b in range(nb):
-        sc_l, box_l, src_l, lab_l = [], [], [], []
-        for l, ((h, w), s) in enumerate(zip(hw, strides)):
-            flat = cls[l][b].reshape(-1)
-            idx = np.nonzero(flat > np.float32(thr))[0]
-            order = np.argsort(-flat[idx], kind='stable')[:nms_pre]
-            idx = idx[order]
-            p, lab = idx // nc, idx % nc
-            px, py = ((p % w) * s).astype(np.float32), ((p // w) * s).astype(np.float32)
-            dist = reg[l][b].reshape(-1, 4)[p] * np.float32(s)
-            x1 = np.clip(px - dist[:, 0], 0, np.float32(clamp_w)) * sx; y1 = np.clip(py - dist[:, 1], 0, np.float32(clamp_h)) * sy
-            x2 = np.clip(px + dist[:, 2], 0, np.float32(clamp_w)) * sx; y2 = np.clip(py + dist[:, 3], 0, np.float32(clamp_h)) * sy
-            sc_l.append(flat[idx]); box_l.append(np.stack([x1, y1, x2, y2], 1).astype(np.float32)); src_l.append(prior0[l] + p); lab_l.append(lab)
-        sc, bx, sr, lb = np.concatenate(sc_l), np.concatenate(box_l), np.concatenate(src_l), np.concatenate(lab_l)
-        ok = ((bx[:, 2] - bx[:, 0]) > np.float32(min_box)) & ((bx[:, 3] - bx[:, 1]) > np.float32(min_box))
-        assert 0 < ok.sum() < len(ok)
-        sc, bx, sr, lb = sc[ok], bx[ok], sr[ok], lb[ok]
-        order = np.argsort(-sc, kind='stable')
-        sc, bx, sr, lb = sc[order], bx[order], sr[order], lb[order]
+        sc, bx, sr, lb, n_before = decode_reference([c[b] for c in cls], [r[b] for r in reg], hw, strides, nc, nms_pre, thr, clamp_w, clamp_h,
+                                                    sx, sy, min_box)
+        assert 0 < len(sc) < n_before
         n = len(sc)
         got_s = scores[b].cpu().numpy()
         assert np.array_equal(got_s[:n], sc) and (got_s[n:] == -1.0).all()
