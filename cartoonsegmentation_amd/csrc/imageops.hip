@@ -693,7 +693,10 @@ __global__ __launch_bounds__(256) void k_colorize_gray_r(const float *__restrict
     xa = fminf(fmaxf(xa, -1.0f), 256.0f);
     int k = (int)xa;
     k = k < 0 ? 0 : (k > 255 ? 255 : k);
-    out[i] = (uint8_t)(255 - k);          // gray_r LUT: uint8((1 - k/255) * 255) == 255 - k  (checked against matplotlib in tests)
+    // gray_r LUT with bytes=True: uint8((1 - linspace(0, 1, 256)[k]) * 255) in float64, truncated -- one below 255 - k for 38 of the 256
+    // entries (k = 221 -> 33); linspace is k * (1 / 255) with the last point set to 1
+    const double t = k == 255 ? 1.0 : (double)k * (1.0 / 255.0);
+    out[i] = (uint8_t)((1.0 - t) * 255.0);
 }
 
 }  // namespace

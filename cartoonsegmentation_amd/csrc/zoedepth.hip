@@ -50,14 +50,19 @@ __global__ __launch_bounds__(256) void k_zoe_pad_prep(const float *__restrict__ 
     out[idx] = (v - 0.5f) / 0.5f;                        // torchvision Normalize: sub mean, div std
 }
 
-// aten upsample_bicubic2d (A = -0.75, align_corners = false, border-clamped taps)
-__device__ __forceinline__ float cc1(float x, float A) { return ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f; }
-__device__ __forceinline__ float cc2(float x, float A) { return ((A * x - 5.0f * A) * x + 8.0f * A) * x - 4.0f * A; }
-__device__ __forceinline__ void cubic_coeffs(float t, float c[4]) {
-    const float A = -0.75f;
-    c[0] = cc2(t + 1.0f, A); c[1] = cc1(t, A);
-    const float u = 1.0f - t;
-    c[2] = cc1(u, A); c[3] = cc2(u + 1.0f, A);
+// aten upsample_bicubic2d (A = -0.75, align_corners = false, border-clamped taps).  The source coordinate and its fraction t are aten's
+// float32 values; the weights and the two four-tap passes are evaluated in double and rounded once.  In float32 the outer weight
+// ((A x - 5 A) x + 8 A) x - 4 A at x in [1, 2] cancels terms of magnitude 12 to a weight <= 0.07, the four weights sum to 1 only within
+// 1.1e-6 and a constant plane comes back up to 17 ulp off; in double the sum is 1 within 1e-14 and the result is the blend of the
+// float32 taps rounded once (a constant plane comes back to the bit).  A few dozen double operations per output element next to 16
+// gathered loads.
+__device__ __forceinline__ double cc1(double x, double A) { return ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0; }
+__device__ __forceinline__ double cc2(double x, double A) { return ((A * x - 5.0 * A) * x + 8.0 * A) * x - 4.0 * A; }
+__device__ __forceinline__ void cubic_coeffs(float t32, double c[4]) {
+    const double A = -0.75, t = (double)t32;
+    c[0] = cc2(t + 1.0, A); c[1] = cc1(t, A);
+    const double u = 1.0 - t;
+    c[2] = cc1(u, A); c[3] = cc2(u + 1.0, A);
 }
 
 // d [B, 1, h, w] (the head's metric depth at the core's resolution) -> out [B, 1, H, W]: bicubic to the padded size (Hp, Wp) evaluated
@@ -74,18 +79,18 @@ __global__ __launch_bounds__(256) void k_zoe_resize_crop(const float *__restrict
     else {
         const float rx = sw * ((float)px + 0.5f) - 0.5f, ry = sh * ((float)py + 0.5f) - 0.5f;     // cubic: no clamp at 0
         const int ix = (int)floorf(rx), iy = (int)floorf(ry);
-        float cx[4], cy[4];
+        double cx[4], cy[4];
         cubic_coeffs(rx - (float)ix, cx); cubic_coeffs(ry - (float)iy, cy);
-        float rows[4];
+        double rows[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int yy = min(max(iy - 1 + i, 0), h - 1);
             const float *R = P + (int64_t)yy * w;
-            const float x0 = R[min(max(ix - 1, 0), w - 1)], x1 = R[min(max(ix, 0), w - 1)];
-            const float x2 = R[min(max(ix + 1, 0), w - 1)], x3 = R[min(max(ix + 2, 0), w - 1)];
+            const double x0 = R[min(max(ix - 1, 0), w - 1)], x1 = R[min(max(ix, 0), w - 1)];
+            const double x2 = R[min(max(ix + 1, 0), w - 1)], x3 = R[min(max(ix + 2, 0), w - 1)];
             rows[i] = x0 * cx[0] + x1 * cx[1] + x2 * cx[2] + x3 * cx[3];
         }
-        v = rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
+        v = (float)(rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3]);
     }
     out[idx] = mode ? (out[idx] + v) / 2.0f : v;
 }
