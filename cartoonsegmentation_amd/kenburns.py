@@ -805,8 +805,12 @@ def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False
     A path ending in .avi (any letter case) is written as a Motion-JPEG AVI instead: the frames -- a list of BGR numpy frames,
     which is uploaded, or the device tensor [n,H,W,3] of process_kenburns(to_numpy=False) -- are JPEG-encoded on the device
     (ops.jpeg_encode with `quality` and `subsampling`) and only the compressed bytes cross to the host.  With playback each frame
-    is still encoded once; the file holds the reference's seq + seq[::-1][1:-1], 2n - 2 chunks."""
-    if str(video_save_path).lower().endswith('.avi'):
+    is still encoded once; the file holds the reference's seq + seq[::-1][1:-1], 2n - 2 chunks.
+
+    A path ending in .apng (any letter case) is written as a lossless animated PNG the same way (ops.png_streams,
+    video.write_apng; `quality` and `subsampling` do not apply)."""
+    suffix = str(video_save_path).lower()
+    if suffix.endswith('.avi') or suffix.endswith('.apng'):
         from . import video
         if isinstance(npy_frame_list, torch.Tensor):
             frames = npy_frame_list
@@ -814,6 +818,11 @@ def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False
             frames = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in npy_frame_list]))).to('cuda')
         if frames.dim() == 3:
             frames = frames.unsqueeze(0)
+        if suffix.endswith('.apng'):
+            streams, W, H, colour_type = ops.png_streams(frames, bgr=True)
+            order = video.playback_order(len(streams)) if playback else None
+            video.write_apng(video_save_path, streams, W, H, colour_type, fps=25, order=order)
+            return
         jpegs = ops.jpeg_encode(frames, quality=quality, subsampling=subsampling)
         order = video.playback_order(len(jpegs)) if playback else None
         video.write_mjpeg_avi(video_save_path, jpegs, int(frames.shape[2]), int(frames.shape[1]), fps=25, order=order)

@@ -613,6 +613,73 @@ def jpeg_encode(frames, quality=90, subsampling='420'):
     return out
 
 
+# ---- PNG of device images (csrc/png.hip + pngcode.py; utils.io_utils.imwrite, the mask PNGs, video.write_apng) -------------
+PNG_SCRATCH_BYTES = 64 << 20           # images are encoded in chunks whose scratch stays below this (one image is always taken)
+
+
+def png_streams(images, bgr=True):
+    """The zlib streams of png_encode (one `bytes` per image: what a PNG's IDAT or an APNG's fdAT chunk holds) and the geometry:
+    returns (streams, width, height, colour_type)."""
+    if not (isinstance(images, torch.Tensor) and images.is_cuda):
+        raise _lib.CsmError("png_encode: images must be a device tensor; libcsm355 has no CPU path")
+    shape, mask = tuple(images.shape), images.dtype == torch.bool
+    if mask:
+        ok, colour = images.dim() in (2, 3), False
+    else:
+        colour = images.dim() == 4 or (images.dim() == 3 and shape[-1] == 3)
+        ok = images.dtype == torch.uint8 and (images.dim() in (2, 3) or (images.dim() == 4 and shape[-1] == 3))
+    if not ok:
+        raise _lib.CsmError("png_encode: uint8 [n,H,W], [H,W], [n,H,W,3], [H,W,3] or bool [n,H,W], [H,W] expected (got %s %s)"
+                            % (images.dtype, shape))
+    im = images.contiguous()                                # named: alive until the kernels that read it are enqueued
+    im = im.view(torch.uint8) if mask else im
+    if im.dim() == (3 if colour else 2):
+        im = im.unsqueeze(0)
+    n, H, W = (int(v) for v in im.shape[:3])
+    C = 3 if colour else 1
+    if not (1 <= H <= 65535 and 1 <= W <= 65535) or H * (W * C + 1) >= 2 ** 31:
+        raise ValueError("png_encode: H and W must be in [1, 65535] and H * (W * channels + 1) below 2^31 (got %dx%d)" % (H, W))
+    from . import pngcode
+    L, dev, st = _lib.load(), im.device, stream_ptr(im.device)
+    flags = i32((1 if colour and bgr else 0) | (2 if mask else 0))
+    per_image = L.csm_png_scratch_bytes(i32(1), i32(H), i32(W), i32(C))
+    step = max(1, min(PNG_SCRATCH_BYTES // per_image, (2 ** 24 - 1) // H))
+    words = L.csm_png_table_words()
+    out = []
+    for f0 in range(0, n, step):
+        part = im[f0:f0 + step]
+        k = int(part.shape[0])
+        table = torch.empty((k, 288), dtype=torch.int32, device=dev)
+        scratch = torch.empty(L.csm_png_scratch_bytes(i32(k), i32(H), i32(W), i32(C)), dtype=torch.uint8, device=dev)
+        check(L.csm_png_measure(ptr(part), i32(k), i32(H), i32(W), i32(C), flags, ptr(table), ptr(scratch), st), "png_measure")
+        table_h = table.cpu().numpy().view(_np.uint32)      # the one sync: the histograms size every stream exactly
+        rows, spans, total = _np.empty((k, words), _np.uint32), [], 0
+        for j in range(k):
+            code = pngcode.build_code(table_h[j, :286])
+            rows[j] = pngcode.table_row(code, table_h[j, 286], total)
+            spans.append((total, code['bytes']))
+            total += (code['bytes'] + 3) & ~3
+        host_table = torch.from_numpy(rows.view(_np.int32)).to(dev)
+        blob = torch.empty(total, dtype=torch.uint8, device=dev)
+        check(L.csm_png_write(i32(k), i32(H), i32(W), i32(C), ptr(host_table), ptr(blob), i64(total), ptr(scratch), st), "png_write")
+        host = blob.cpu().numpy().tobytes()
+        out += [host[o:o + b] for o, b in spans]
+    return out, W, H, 2 if colour else 0
+
+
+def png_encode(images, bgr=True):
+    """PNG files (8 bit, no interlace, no alpha; contract DESIGN.md §4.7) of device images: uint8 [n,H,W] or [H,W] (grey, colour
+    type 0), uint8 [n,H,W,3] or [H,W,3] (colour type 2; B, G, R in memory unless bgr=False, written R, G, B), or bool [n,H,W] /
+    [H,W] masks (written as 0 / 255 grey).  A uint8 tensor of rank 3 whose last dimension is 3 is one colour image.  Returns a list
+    of n `bytes`, each a complete, lossless PNG.  Filtering, the run parse, the histogram, the Adler-32 and the bit packing run on
+    the device (csm_png_measure / _write) in chunks of images whose scratch stays below PNG_SCRATCH_BYTES; per chunk the host
+    reads the [k,288] histogram table once, builds each image's Huffman code (pngcode.build_code), then reads only the
+    compressed bytes."""
+    from . import pngcode
+    streams, W, H, colour_type = png_streams(images, bgr)
+    return [pngcode.png_file(s, W, H, colour_type) for s in streams]
+
+
 # ---- PatchMatch inpainting (animeinsseg/inpainting/patch_match.py; kenburns_effect.py:497-503) ----------------------------
 def patchmatch_inpaint(img, mask, global_mask=None, patch_size=15, seed=0):
     """PatchMatch inpainting of device uint8 [H,W,3] `img` where the device uint8 `mask` ([H,W] or [H,W,1]) is non-zero;

@@ -277,10 +277,15 @@ class AnimeInsSeg:
         return insts
 
     # ---- COCO annotation export (reference :506-621, :667-693) -------------------------------------------
-    def _infer_save_annotations(self, imgs, pred_score_thr, save_dir, save_annotation, obj_id_start, img_id_start, val_dir):
+    def _infer_save_annotations(self, imgs, pred_score_thr, save_dir, save_annotation, obj_id_start, img_id_start, val_dir,
+                                save_mask_only: bool = False):
         """infer every image and write the COCO instance-segmentation file `save_annotation`; returns None.  Frames run in chunks of
         det_batch (the batched detector / refine when a chunk's frames are equally sized); each chunk's masks are RLE-encoded on the
-        device (ops.mask_rle_encode) and released before the next chunk, and no mask is copied to the host."""
+        device (ops.mask_rle_encode) and released before the next chunk, and no mask is copied to the host.
+
+        save_mask_only (reference :597-598, :616): instead of the file, one 0 / 255 grey `mask_{ii:03d}_{img_name}.png` per instance
+        in save_dir, PNG-encoded on the device (ops.png_encode); no JSON is written.  infer() does not forward it, as in the
+        reference."""
         from utils.constants import CATEGORIES
         from utils.io_utils import dict2json, find_all_imgs, imread
         from . import ops
@@ -312,7 +317,12 @@ class AnimeInsSeg:
                     image_id = imgp2ids[src]
                 im_h, im_w = (int(v) for v in frame.shape[:2])
                 image_meta.append({"id": image_id, "height": im_h, "width": im_w, "file_name": img_name})
-                if not inst.is_empty:
+                if save_mask_only:
+                    if not inst.is_empty:
+                        for j, data in enumerate(ops.png_encode(inst.masks.bool())):
+                            with open(os.path.join(save_dir, 'mask_' + str(j).zfill(3) + '_' + img_name + '.png'), 'wb') as f:
+                                f.write(data)
+                elif not inst.is_empty:
                     counts, areas = ops.mask_rle_encode(inst.masks)
                     size = [int(inst.masks.shape[1]), int(inst.masks.shape[2])]         # the mask's shape, as the reference encodes it
                     scores = inst.scores.tolist()
@@ -325,8 +335,9 @@ class AnimeInsSeg:
                         obj_id += 1
                 image_id += 1
             del insts, frames
-        dict2json({"info": {}, "licenses": [], "images": image_meta, "annotations": det_annotations, "categories": CATEGORIES},
-                  save_annotation)
+        if not save_mask_only:
+            dict2json({"info": {}, "licenses": [], "images": image_meta, "annotations": det_annotations, "categories": CATEGORIES},
+                      save_annotation)
         return None
 
     # ---- detector forward + post-process (reference :447-462 + mmdet predict_by_feat) ---------------

@@ -1,5 +1,5 @@
-"""Motion-JPEG AVI container (pure host code): the video file of the Ken Burns path, from frames that ops.jpeg_encode
-compressed on the device.
+"""Motion-JPEG AVI container and animated-PNG container (pure host code): the video files of the Ken Burns path, from frames
+that ops.jpeg_encode / ops.png_streams compressed on the device.
 
 A classic RIFF AVI (AVI 1.0, no OpenDML extension, so below 2 GiB):
 
@@ -12,6 +12,13 @@ A classic RIFF AVI (AVI 1.0, no OpenDML extension, so below 2 GiB):
       LIST 'movi'
         '00dc' <JPEG file> ...          one chunk per output frame, padded to an even size
       'idx1'  16 B per chunk: '00dc', AVIIF_KEYFRAME, offset from the 'movi' fourcc, size
+
+An APNG (APNG specification 1.0) is a PNG whose first frame is the default image:
+
+    signature, IHDR, acTL (frames, plays = 0: for ever)
+    fcTL (sequence 0), IDAT <zlib stream of frame 0>
+    fcTL, fdAT <sequence number + zlib stream> ...      per further output frame; sequence numbers count fcTL and fdAT together
+    IEND
 """
 import struct
 
@@ -71,3 +78,34 @@ def write_mjpeg_avi(path, jpegs, width, height, fps=25, order=None):
             f.write(_chunk(b'00dc', jpegs[i]))
         f.write(_chunk(b'idx1', b''.join(index)))
     return riff_bytes + 8
+
+
+def write_apng(path, streams, width, height, colour_type, fps=25, order=None):
+    """Write the zlib streams `streams` (a list of bytes from ops.png_streams, all width x height of `colour_type` 0 grey or 2 RGB)
+    as a lossless animated PNG that shows every frame for 1 / fps seconds and loops for ever.  `order` as in write_mjpeg_avi: a
+    frame is encoded once and may be written several times.  Every frame covers the whole canvas (dispose NONE, blend SOURCE).
+    Returns the number of bytes written."""
+    from .pngcode import PNG_SIGNATURE, chunk, ihdr
+    order = list(range(len(streams))) if order is None else [int(i) for i in order]
+    if not order:
+        raise ValueError("write_apng: at least one frame is needed")
+    if any(i < 0 or i >= len(streams) for i in order):
+        raise ValueError("write_apng: order refers to a frame outside the %d encoded ones" % len(streams))
+    width, height, fps = int(width), int(height), int(fps)
+    if not (1 <= width <= 65535 and 1 <= height <= 65535 and 1 <= fps <= 65535 and colour_type in (0, 2)):
+        raise ValueError("write_apng: width, height and fps must be in [1, 65535] and colour_type 0 or 2")
+    parts = [PNG_SIGNATURE, ihdr(width, height, colour_type), chunk(b'acTL', struct.pack('>II', len(order), 0))]
+    seq = 0
+    for k, i in enumerate(order):
+        parts.append(chunk(b'fcTL', struct.pack('>IIIIIHHBB', seq, width, height, 0, 0, 1, fps, 0, 0)))
+        seq += 1
+        if k == 0:
+            parts.append(chunk(b'IDAT', streams[i]))
+        else:
+            parts.append(chunk(b'fdAT', struct.pack('>I', seq) + streams[i]))
+            seq += 1
+    parts.append(chunk(b'IEND', b''))
+    data = b''.join(parts)
+    with open(path, 'wb') as f:
+        f.write(data)
+    return len(data)

@@ -512,6 +512,33 @@ int csm_jpeg_measure(const uint8_t *frames, int n, int H, int W, int quality, in
 int csm_jpeg_write(int n, int H, int W, int quality, int subsampling, const int64_t *info, uint8_t *out, void *scratch,
                    void *stream);
 
+/* The zlib stream of a PNG's IDAT chunk for n equally sized 8-bit images (png.hip; contract DESIGN.md §4.7, restated in
+ * tests/png_restatement.py, byte-identical).  images u8 [n,H,W,channels], contiguous; channels 1 (grey) or 3; 1 <= H, W <= 65535,
+ * H * (W * channels + 1) < 2^31 and n * H < 2^24.  flags: bit 0 = the three channels are B, G, R in memory (written R, G, B), bit 1 =
+ * grey bytes are a mask (any non-zero byte is written as 255).  Per scanline the best of the five PNG filters; per image ONE
+ * deflate block of literals and distance-1 matches, whose Huffman code the HOST builds between the two calls.
+ * scratch: csm_png_scratch_bytes(n, H, W, channels) device bytes, shared by the two calls: the filtered scanlines
+ *   (W * channels + 1 bytes each) and 20 B per scanline.  0 for an invalid shape.  No scanline is staged in LDS, so there is no
+ *   width bound and no second path.
+ * csm_png_measure: table device uint32 [n][288] = the counts of the 286 literal / length symbols (the end-of-block symbol counted
+ *   once), the Adler-32 of the filtered bytes, one spare word.
+ * csm_png_write: host_table device uint32 [n][csm_png_table_words() = 384], filled by the host from the measured table:
+ *   [0..285] bit-reversed code | code length << 16 of every symbol, [286] bits of the header (the two zlib bytes + the block
+ *   header), [287] the Adler-32, [288..289] byte offset of the stream in out (low, high word; a multiple of 4), [290] bits of a
+ *   match's all-zero distance code (1 under the dynamic code, 5 under the fixed one), [291] bytes of the stream, [292..383] the
+ *   header bits, LSB-first.  out: out_bytes device bytes (a multiple of 4, 4-aligned), zeroed by the call; image f's stream at its
+ *   offset: header, every scanline's symbols at its bit offset, the end-of-block symbol, zero bits to the next byte, the Adler-32
+ *   big-endian.  Nothing is written at or past the stream's bytes rounded up to 4.  Same n, H, W, channels and scratch as the
+ *   measure call.
+ * Three launches and a memset per call, async on the stream, no allocation, no sync; the only atomics are integer adds (counts)
+ * and integer ORs of disjoint bits, so the output is deterministic. */
+size_t csm_png_scratch_bytes(int n, int H, int W, int channels);
+int csm_png_table_words(void);
+int csm_png_measure(const uint8_t *images, int n, int H, int W, int channels, int flags, uint32_t *table, void *scratch,
+                    void *stream);
+int csm_png_write(int n, int H, int W, int channels, const uint32_t *host_table, uint8_t *out, int64_t out_bytes, void *scratch,
+                  void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */

@@ -1,6 +1,6 @@
 """reference utils/io_utils.py -- the image helpers on the hot path's edge: find_all_imgs (:92-103), scaledown_maxsize
-(:254-274), resize_pad (:277-292), plus imread (mmcv.imread stand-in: the reference's callers decode with mmcv / cv2, which this
-image does not have).  The resamplers run on the MI355X (cv2's uint8 INTER_LINEAR arithmetic restated in imageops.hip).
+(:254-274), resize_pad (:277-292), plus imread / imwrite (mmcv.imread / mmcv.imwrite stand-ins: the reference's callers decode and
+encode with mmcv / cv2, which this image does not have; imwrite compresses on the MI355X, csrc/png.hip and csrc/mjpeg.hip).  The resamplers run on the MI355X (cv2's uint8 INTER_LINEAR arithmetic restated in imageops.hip).
 The annotation helpers: NumpyEncoder / json2dict / dict2json (:24-47), mask2rle (:327-333; the RLE is built on the MI355X,
 csrc/maskrle.hip) and read_imglst_from_txt (animeinsseg/__init__.py:179-183)."""
 import json
@@ -28,6 +28,34 @@ def imread(path):
     with Image.open(path) as im:
         im = ImageOps.exif_transpose(im).convert('RGB')
         return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
+
+
+def imwrite(img, file_path, auto_mkdir=True):
+    """mmcv.imwrite / cv2.imwrite stand-in: `img` is a BGR [H,W,3] or grey [H,W] uint8 image, a numpy array (uploaded) or a device
+    tensor; it is compressed on the MI355X and only the file's bytes reach the host.  .png: lossless (ops.png_encode); .jpg /
+    .jpeg: ops.jpeg_encode at cv2's defaults (quality 95, 4:2:0; colour only).  Any other suffix raises ValueError.  Returns
+    True."""
+    suffix = Path(str(file_path)).suffix.lower()
+    if suffix not in ('.png', '.jpg', '.jpeg'):
+        raise ValueError("imwrite: %r is not written here (.png, .jpg and .jpeg are)" % suffix)
+    import torch
+    from cartoonsegmentation_amd import ops
+    t = img if isinstance(img, torch.Tensor) else torch.tensor(np.asarray(img)).cuda()
+    if t.dim() == 3 and t.shape[2] == 1:
+        t = t[:, :, 0]
+    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 3):
+        raise ValueError("imwrite: an [H,W] or [H,W,3] image is expected (got shape %s)" % (tuple(t.shape),))
+    if suffix == '.png':
+        data = ops.png_encode(t.unsqueeze(0), bgr=True)[0]
+    else:
+        if t.dim() == 2:
+            raise ValueError("imwrite: the JPEG encoder takes colour images [H,W,3] only")
+        data = ops.jpeg_encode(t, quality=95, subsampling='420')[0]
+    if auto_mkdir:
+        os.makedirs(osp.dirname(osp.abspath(str(file_path))), exist_ok=True)
+    with open(file_path, 'wb') as f:
+        f.write(data)
+    return True
 
 
 def scaledown_size(im_h, im_w, max_size, divisior=None):
