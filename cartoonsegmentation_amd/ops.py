@@ -613,6 +613,84 @@ def jpeg_encode(frames, quality=90, subsampling='420'):
     return out
 
 
+# ---- baseline JPEG files to device frames (csrc/jpegdec.hip + jpegcode.py; utils.io_utils.imread_device) -------------------
+JPEG_DECODE_SCRATCH_BYTES = 64 << 20   # files are decoded in chunks whose scratch stays below this (one file is always taken)
+
+
+def jpeg_decode(files, device=None, stats=None, _infos=None):
+    """Baseline JPEG files (contract DESIGN.md §4.8) to device uint8 [H,W,3] tensors in B, G, R order.  `files` is one `bytes` (one
+    tensor is returned) or a list of `bytes` (a list is returned); sizes and modes (grey, 4:4:4, 4:2:2, 4:2:0, with or without
+    restart markers) may differ within a call.  A grey file gives three equal channels.  EXIF orientation is NOT applied.  The
+    host parses the markers (jpegcode.probe; a stream the decoder does not take raises jpegcode.Unsupported) and uploads only the
+    files' entropy bytes and tables; Huffman decoding, the inverse DCT, chroma upsampling and colour conversion run on the device
+    (csm_jpeg_decode) in chunks of files whose scratch stays below JPEG_DECODE_SCRATCH_BYTES.  Corrupt entropy data raises
+    CsmError.  The tensors of a chunk are views of one allocation.  `stats` (a dict) receives 'passes': the synchronisation passes
+    between workgroups of every chunk."""
+    import ctypes
+    from . import jpegcode
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    datas = [files] if single else list(files)
+    for d in datas:
+        if not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError("jpeg_decode: bytes or a list of bytes expected (got %s)" % type(d).__name__)
+    infos = _infos if _infos is not None else [jpegcode.probe(d) for d in datas]
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.CsmError("jpeg_decode: the device must be a GPU (got %s); libcsm355 has no CPU path" % dev)
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    L = _lib.load()
+    words = L.csm_jpeg_decode_desc_words()
+    assert words == jpegcode.DESC_WORDS
+    c_desc = ctypes.POINTER(ctypes.c_int32)
+
+    def scratch_bytes(desc):
+        return L.csm_jpeg_decode_scratch_bytes(desc.ctypes.data_as(c_desc), i32(desc.shape[0]))
+
+    own = [scratch_bytes(jpegcode.descriptor(info, 0, 0, 0).reshape(1, -1)) for info in infos]
+    out, passes = [], []
+    i = 0
+    while i < len(datas):
+        k, total = 1, own[i]
+        while i + k < len(datas) and total + own[i + k] <= JPEG_DECODE_SCRATCH_BYTES:
+            total += own[i + k]
+            k += 1
+        part = list(zip(datas[i:i + k], infos[i:i + k]))
+        i += k
+        # the blob: every file's table region, then every file's entropy bytes, each on a 16-byte boundary
+        ent_off, o = [], k * jpegcode.FILE_TABLE_BYTES
+        for _, info in part:
+            ent_off.append(o)
+            o += (info['entropy'][1] - info['entropy'][0] + 15) & ~15
+        blob_h = _np.zeros(max(o, 16), _np.uint8)
+        desc = _np.zeros((k, words), _np.int32)
+        out_off, oo = [], 0
+        for j, (d, info) in enumerate(part):
+            blob_h[j * jpegcode.FILE_TABLE_BYTES:(j + 1) * jpegcode.FILE_TABLE_BYTES] = jpegcode.file_tables(info)
+            s, e = info['entropy']
+            blob_h[ent_off[j]:ent_off[j] + e - s] = _np.frombuffer(d, _np.uint8, e - s, s)
+            desc[j] = jpegcode.descriptor(info, ent_off[j], j * jpegcode.FILE_TABLE_BYTES, oo)
+            out_off.append(oo)
+            oo += (info['height'] * info['width'] * 3 + 15) & ~15
+        with torch.cuda.device(dev):
+            blob = torch.from_numpy(blob_h).to(dev)
+            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
+            need = scratch_bytes(desc)
+            if need == 0:
+                raise _lib.CsmError("jpeg_decode: %s" % L.csm_last_error().decode())
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+            info_h = (ctypes.c_int * 4)()
+            check(L.csm_jpeg_decode(ptr(blob), i64(blob.numel()), desc.ctypes.data_as(c_desc), i32(k), ptr(pixels), i64(oo),
+                                    ptr(scratch), info_h, stream_ptr(dev)), "jpeg_decode")
+        passes.append(int(info_h[0]))
+        for j, (_, info) in enumerate(part):
+            H, W = info['height'], info['width']
+            out.append(pixels[out_off[j]:out_off[j] + H * W * 3].view(H, W, 3))
+    if stats is not None:
+        stats['passes'] = passes
+    return out[0] if single else out
+
+
 # ---- PNG of device images (csrc/png.hip + pngcode.py; utils.io_utils.imwrite, the mask PNGs, video.write_apng) -------------
 PNG_SCRATCH_BYTES = 64 << 20           # images are encoded in chunks whose scratch stays below this (one image is always taken)
 

@@ -168,6 +168,7 @@ class AnimeInsSeg:
         self.refine_method = None
         self.refine_batch = int(os.environ.get('CSM_REFINE_BATCH', '16'))   # instances per ISNet run when frames are batched
         self.det_batch = max(1, int(os.environ.get('CSM_DET_BATCH', '16')))  # frames per detector run (longer lists are chunked)
+        self.device_decode = os.environ.get('CSM_DEVICE_DECODE', '0') == '1'  # path inputs: baseline JPEGs are decoded on the device
         self.set_refine_method(**(refine_kwargs or {'refine_method': 'none'}))
 
     # ---- configuration (reference :395-399, :623-636, :704-708) --------------------------------
@@ -256,8 +257,7 @@ class AnimeInsSeg:
     def _infer_frames(self, imgs, pred_score_thr):
         """detector + refine of a list of images (paths or BGR arrays) -> AnimeInstances with device masks"""
         if any(isinstance(im, str) for im in imgs):               # single_image_preprocess, reference :62-64: mmcv.imread(path)
-            from utils.io_utils import imread
-            imgs = [imread(im) if isinstance(im, str) else im for im in imgs]
+            imgs = self._load(imgs)
         same = len(imgs) > 1 and all(tuple(im.shape) == tuple(imgs[0].shape) for im in imgs)
         if same:            # equally sized frames: one batched detector run + refine batches shared across frames
             insts = [self._instances_from(d, pred_score_thr) for d in self.detect_raw_batch(imgs)]
@@ -276,6 +276,20 @@ class AnimeInsSeg:
                 insts.append(inst)
         return insts
 
+    def _load(self, imgs):
+        """the path entries of `imgs` as images: imread (host, PIL), or with device_decode imread_device_many, one call per det_batch
+        chunk (baseline JPEGs are then decoded on the device; every other file still goes through imread)"""
+        from utils.io_utils import imread, imread_device_many
+        if not self.device_decode:
+            return [imread(im) if isinstance(im, str) else im for im in imgs]
+        out = list(imgs)
+        where = [i for i, im in enumerate(imgs) if isinstance(im, str)]
+        for c0 in range(0, len(where), self.det_batch):
+            part = where[c0:c0 + self.det_batch]
+            for i, t in zip(part, imread_device_many([imgs[i] for i in part], self.device)):
+                out[i] = t
+        return out
+
     # ---- COCO annotation export (reference :506-621, :667-693) -------------------------------------------
     def _infer_save_annotations(self, imgs, pred_score_thr, save_dir, save_annotation, obj_id_start, img_id_start, val_dir,
                                 save_mask_only: bool = False):
@@ -287,7 +301,7 @@ class AnimeInsSeg:
         in save_dir, PNG-encoded on the device (ops.png_encode); no JSON is written.  infer() does not forward it, as in the
         reference."""
         from utils.constants import CATEGORIES
-        from utils.io_utils import dict2json, find_all_imgs, imread
+        from utils.io_utils import dict2json, find_all_imgs
         from . import ops
         imgp2ids = None
         if isinstance(imgs, str) and imgs.endswith('.json'):
@@ -309,7 +323,7 @@ class AnimeInsSeg:
         obj_id, image_id = obj_id_start + 1, img_id_start + 1
         for c0 in range(0, len(imgs), self.det_batch):
             chunk = imgs[c0:c0 + self.det_batch]
-            frames = [imread(im) if isinstance(im, str) else im for im in chunk]
+            frames = self._load(chunk)
             insts = self._infer_frames(frames, pred_score_thr)
             for k, (src, frame, inst) in enumerate(zip(chunk, frames, insts)):
                 img_name = os.path.basename(src) if isinstance(src, str) else f'{c0 + k}'.zfill(12) + '.jpg'

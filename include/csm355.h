@@ -26,6 +26,7 @@ extern "C" {
 #define CSM_ERR_ARG 1
 #define CSM_ERR_HIP 2
 #define CSM_ERR_NAN 3
+#define CSM_ERR_DATA 4   /* corrupt input data (csm_jpeg_decode) */
 
 /* thread-local message of the last non-zero status */
 const char *csm_last_error(void);
@@ -538,6 +539,31 @@ int csm_png_measure(const uint8_t *images, int n, int H, int W, int channels, in
                     void *stream);
 int csm_png_write(int n, int H, int W, int channels, const uint32_t *host_table, uint8_t *out, int64_t out_bytes, void *scratch,
                   void *stream);
+
+/* Baseline JPEG files to uint8 B, G, R pixels (jpegdec.hip; contract DESIGN.md §4.8, restated in tests/jpegdec_restatement.py,
+ * byte-identical).  The host parses the markers (cartoonsegmentation_amd/jpegcode.py) and hands over one blob of device bytes and
+ * one descriptor per file; files of different sizes and modes share a call.
+ * desc_host: host int32 [n][csm_jpeg_decode_desc_words() = 20]: [0] H, [1] W, [2] components (1 grey, 3 Y Cb Cr), [3] [4] the
+ *   luminance sampling factors (1x1, 2x1 or 2x2; chroma is 1x1), [5] restart interval in MCUs (0 = none), [6] [7] offset and length of
+ *   the entropy-coded bytes in the blob, [8] offset (a multiple of 4) of the file's table region in the blob, [9..11] / [12..14] the
+ *   slot (0..5) of each component's DC / AC Huffman table, [15] [16] the byte offset of the file's pixels in out (low 31 bits,
+ *   the bits above; a multiple of 4), the rest 0.
+ * table region (5856 bytes): six Huffman tables of 912 bytes (uint16 lut[256]: length << 8 | symbol of the codes of up to 8 bits
+ *   by the next 8 bits, else 0; int32 maxcode[18] by length, -1 = none; int32 valoff[18]: symbol index = valoff[length] + code;
+ *   uint8 vals[256]), then uint16 [3][64] quantisation tables per component in natural order.
+ * out: u8, file i at its offset as [H][W][3].  blob, out and scratch are 16-byte aligned.
+ * scratch: csm_jpeg_decode_scratch_bytes(desc_host, n) device bytes (0 for invalid descriptors): 28 B per subsequence, int16
+ *   coefficients and uint8 sample planes of the padded components.
+ * csm_jpeg_decode_subseq_bytes: bytes of entropy data one lane owns (a compile-time constant).
+ * csm_jpeg_decode: info_host (may be NULL) receives [0] the number of synchronisation passes between workgroups.  The call
+ *   SYNCHRONISES the stream: once per pass (it reads a 4-byte flag) and once at the end (one error word per file).  Returns
+ *   CSM_ERR_DATA for corrupt entropy data; whatever the data, no read leaves a file's entropy bytes and no store its blocks.
+ *   No kernel waits on another workgroup; the output is deterministic. */
+size_t csm_jpeg_decode_scratch_bytes(const int32_t *desc_host, int n);
+int csm_jpeg_decode_subseq_bytes(void);
+int csm_jpeg_decode_desc_words(void);
+int csm_jpeg_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
+                    void *scratch, int *info_host, void *stream);
 
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW

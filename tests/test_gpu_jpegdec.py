@@ -1,0 +1,134 @@
+"""GPU: ops.jpeg_decode (csrc/jpegdec.hip) equals the numpy restatement of its contract (tests/jpegdec_restatement.py, DESIGN.md
+§4.8) byte for byte over the files of tests/jpegdec_cases.py, and utils.io_utils.imread_device / AnimeInsSeg.device_decode route
+files as documented."""
+import io
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+Image = pytest.importorskip("PIL.Image")
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import jpegdec_cases as C  # noqa: E402
+from cartoonsegmentation_amd import _lib, jpegcode, ops  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+def decoded(data):
+    t = ops.jpeg_decode(data)
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    return t.cpu().numpy()
+
+
+@pytest.mark.parametrize("case", C.CASES, ids=C.case_id)
+def test_decode_equals_the_restatement(case):
+    data = C.case_file(case)
+    info = jpegcode.probe(data)                   # every case must be one the decoder takes: none drops out silently
+    assert (info['height'], info['width']) == (case['H'], case['W'])
+    _, _, want = C.reference(data)
+    assert np.array_equal(decoded(data), want)
+
+
+def test_the_largest_case_spans_workgroups():
+    S = _lib.load().csm_jpeg_decode_subseq_bytes()
+    big = [c for c in C.CASES if (c['H'], c['W']) == (192, 256) and c['mode'] != 'grey']
+    for c in big:
+        s, e = jpegcode.probe(C.case_file(c))['entropy']
+        assert (e - s) / S > 256, C.case_id(c)
+    stats = {}
+    ops.jpeg_decode([C.case_file(big[0])], stats=stats)
+    assert stats['passes'][0] >= 1
+
+
+@pytest.mark.parametrize("kind", C.SPECIAL_KINDS)
+def test_stuffing_and_markers_on_subsequence_boundaries(kind):
+    S = int(_lib.load().csm_jpeg_decode_subseq_bytes())
+    data = C.special_file(kind, S)
+    assert C.has_property(kind, data, S)
+    assert np.array_equal(decoded(data), C.reference(data)[2])
+
+
+def test_six_files_in_one_call_equal_six_calls():
+    pick = [c for c in C.CASES if (c['H'], c['W']) in ((24, 40), (33, 17), (1, 1))][:5] + \
+           [next(c for c in C.CASES if c['content'] == 'noise' and c['mode'] == '420')]
+    assert len(pick) == 6 and len({(c['H'], c['W'], c['mode']) for c in pick}) >= 5
+    files = [C.case_file(c) for c in pick]
+    together = ops.jpeg_decode(files)
+    assert isinstance(together, list) and len(together) == 6
+    for c, data, t in zip(pick, files, together):
+        assert tuple(t.shape) == (c['H'], c['W'], 3)
+        assert torch.equal(t, ops.jpeg_decode(data)), C.case_id(c)
+        assert np.array_equal(t.cpu().numpy(), C.reference(data)[2]), C.case_id(c)
+
+
+def test_a_file_larger_than_the_scratch_chunk(monkeypatch):
+    """one 1024 x 1024 frame between two small files, with the chunk budget below the large file's scratch: it is taken alone"""
+    img = C.frame('cartoon', 1024, 1024, 4)
+    big = C.pil_jpeg(img, '420', quality=50)
+    small = C.case_file(C.CASES[13])
+    monkeypatch.setattr(ops, 'JPEG_DECODE_SCRATCH_BYTES', 1 << 20)
+    stats = {}
+    out = ops.jpeg_decode([small, big, small], stats=stats)
+    assert len(stats['passes']) == 3
+    assert np.array_equal(out[1].cpu().numpy(), C.reference(big)[2])
+    assert np.array_equal(out[0].cpu().numpy(), C.reference(small)[2]) and torch.equal(out[0], out[2])
+
+
+def test_errors():
+    with pytest.raises(jpegcode.Unsupported):
+        ops.jpeg_decode(C.pil_jpeg(C.frame('cartoon', 16, 16, 0), '420', progressive=True))
+    with pytest.raises(TypeError):
+        ops.jpeg_decode(["not bytes"])
+    with pytest.raises(_lib.CsmError):
+        ops.jpeg_decode(C.case_file(C.CASES[0]), device='cpu')
+    assert ops.jpeg_decode([]) == []
+
+
+def test_imread_device_routes_files(tmp_path):
+    from utils.io_utils import imread, imread_device, imread_device_many
+    img = C.frame('cartoon', 40, 56, 5)
+    exif = Image.Exif()
+    exif[0x0112] = 6
+    files = {'base.jpg': C.pil_jpeg(img, '420'), 'grey.JPEG': C.pil_jpeg(img, 'grey'),
+             'prog.jpg': C.pil_jpeg(img, '420', progressive=True), 'rot.jpg': C.pil_jpeg(img, '422', exif=exif.tobytes())}
+    for name, data in files.items():
+        (tmp_path / name).write_bytes(data)
+    buf = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(buf, 'PNG')
+    (tmp_path / 'pic.png').write_bytes(buf.getvalue())
+    for name in ('base.jpg', 'grey.JPEG'):                    # the device decode
+        t = imread_device(str(tmp_path / name))
+        assert torch.equal(t, ops.jpeg_decode(files[name])) and tuple(t.shape) == (40, 56, 3)
+    for name in ('pic.png', 'prog.jpg', 'rot.jpg'):           # imread + upload
+        t = imread_device(str(tmp_path / name))
+        assert t.is_cuda and np.array_equal(t.cpu().numpy(), imread(str(tmp_path / name))), name
+    assert tuple(imread_device(str(tmp_path / 'rot.jpg')).shape) == (56, 40, 3)
+    names = ['pic.png', 'base.jpg', 'rot.jpg', 'grey.JPEG']
+    many = imread_device_many([str(tmp_path / n) for n in names])
+    for n, t in zip(names, many):
+        assert torch.equal(t, imread_device(str(tmp_path / n))), n
+
+
+def test_export_with_device_decode_lists_the_same_images(tmp_path, monkeypatch):
+    from animeinsseg import AnimeInsSeg
+    src = tmp_path / 'in'
+    src.mkdir()
+    for k, mode in enumerate(('420', '444', 'grey')):
+        (src / ('f%d.jpg' % k)).write_bytes(C.pil_jpeg(C.frame('cartoon', 64, 80, 10 + k), mode))
+    images = {}
+    for flag in ('0', '1'):
+        monkeypatch.setenv('CSM_DEVICE_DECODE', flag)
+        net = AnimeInsSeg('synthetic', default_det_size=64, refine_kwargs={'refine_method': 'refinenet_isnet', 'refine_size': 48})
+        assert net.device_decode == (flag == '1')
+        out = tmp_path / ('out%s.json' % flag)
+        net.infer(str(src), save_annotation=str(out), save_dir=str(tmp_path / ('sd' + flag)), pred_score_thr=0.3, max_instances=2)
+        images[flag] = json.loads(out.read_text())['images']
+    assert len(images['0']) == 3 and all(im['height'] == 64 and im['width'] == 80 for im in images['0'])
+    assert images['0'] == images['1']
+    monkeypatch.delenv('CSM_DEVICE_DECODE')
+    assert AnimeInsSeg('synthetic', default_det_size=64).device_decode is False

@@ -30,6 +30,40 @@ def imread(path):
         return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
 
 
+def imread_device_many(paths, device=None):
+    """imread for a list of paths with the pixels on the device: a list of uint8 BGR [H,W,3] tensors.  A .jpg / .jpeg file that the
+    device decoder takes (cartoonsegmentation_amd.jpegcode.probe: baseline, Huffman, grey or Y Cb Cr at 4:4:4 / 4:2:2 / 4:2:0) and
+    whose EXIF orientation is 1 or absent is decoded on the MI355X by ops.jpeg_decode, all such files in one call: only the file's
+    bytes are uploaded.  Every other file (PNG, BMP, progressive or rotated JPEG, ...) goes through imread and an upload.  The
+    device decode follows the contract of DESIGN.md §4.8."""
+    import torch
+    from cartoonsegmentation_amd import jpegcode, ops
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    out = [None] * len(paths)
+    idx, datas, infos = [], [], []
+    for i, path in enumerate(paths):
+        if Path(str(path)).suffix.lower() in ('.jpg', '.jpeg'):
+            with open(path, 'rb') as f:
+                data = f.read()
+            try:
+                info = jpegcode.probe(data)
+            except jpegcode.Unsupported:
+                info = None
+            if info is not None and info['orientation'] in (None, 1):
+                idx.append(i); datas.append(data); infos.append(info)
+                continue
+        out[i] = torch.from_numpy(imread(path)).to(dev)
+    if datas:
+        for i, t in zip(idx, ops.jpeg_decode(datas, dev, _infos=infos)):
+            out[i] = t
+    return out
+
+
+def imread_device(path, device=None):
+    """imread with the pixels on the device: see imread_device_many"""
+    return imread_device_many([path], device)[0]
+
+
 def imwrite(img, file_path, auto_mkdir=True):
     """mmcv.imwrite / cv2.imwrite stand-in: `img` is a BGR [H,W,3] or grey [H,W] uint8 image, a numpy array (uploaded) or a device
     tensor; it is compressed on the MI355X and only the file's bytes reach the host.  .png: lossless (ops.png_encode); .jpg /
