@@ -691,6 +691,83 @@ def jpeg_decode(files, device=None, stats=None, _infos=None):
     return out[0] if single else out
 
 
+# ---- PNG files to device frames (csrc/pngdec.hip + pngread.py; utils.io_utils.imread_device) ------------------------------------
+PNG_DECODE_SCRATCH_BYTES = 512 << 20   # files are decoded in chunks whose scratch stays below this (one file is always taken)
+
+
+def png_decode(files, device=None, stats=None, _infos=None):
+    """PNG files (contract DESIGN.md §4.9) to device uint8 [H,W,3] tensors in B, G, R order, equal to utils.io_utils.imread on every
+    byte.  `files` is one `bytes` (one tensor is returned) or a list of `bytes` (a list is returned); sizes and colour types (grey,
+    RGB, palette, grey + alpha, RGBA; 8 bits, not interlaced) may differ within a call.  Alpha is dropped, grey gives three equal
+    channels.  The host walks the chunks (pngread.probe; a file the decoder does not take raises pngread.Unsupported) and uploads
+    only the IDAT payloads and the palettes; inflate, the unfiltering and the colour conversion run on the device
+    (csm_png_decode) in chunks of files whose scratch stays below PNG_DECODE_SCRATCH_BYTES.  A corrupt stream (invalid deflate
+    data, a wrong Adler-32, a filter type above 4) raises CsmError.  The tensors of a chunk are views of one allocation.  `stats`
+    (a dict) receives 'rounds': per chunk, the pointer-doubling rounds (launched, that did work)."""
+    import ctypes
+    from . import pngread
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    datas = [files] if single else list(files)
+    for d in datas:
+        if not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError("png_decode: bytes or a list of bytes expected (got %s)" % type(d).__name__)
+    infos = _infos if _infos is not None else [pngread.probe(d) for d in datas]
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.CsmError("png_decode: the device must be a GPU (got %s); libcsm355 has no CPU path" % dev)
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    L = _lib.load()
+    words = L.csm_png_decode_desc_words()
+    assert words == pngread.DESC_WORDS
+    c_desc = ctypes.POINTER(ctypes.c_int32)
+
+    def scratch_bytes(desc):
+        return L.csm_png_decode_scratch_bytes(desc.ctypes.data_as(c_desc), i32(desc.shape[0]))
+
+    own = [scratch_bytes(pngread.descriptor(info, 0, 0, 0).reshape(1, -1)) for info in infos]
+    out, rounds = [], []
+    i = 0
+    while i < len(datas):
+        k, total = 1, own[i]
+        while i + k < len(datas) and total + own[i + k] <= PNG_DECODE_SCRATCH_BYTES:
+            total += own[i + k]
+            k += 1
+        part = list(zip(datas[i:i + k], infos[i:i + k]))
+        i += k
+        # the blob: every file's palette (768 bytes), then every file's zlib stream, each on a 16-byte boundary and padded to one
+        stream_off, o = [], k * 768
+        for _, info in part:
+            stream_off.append(o)
+            o += (info['stream_bytes'] + 15) & ~15
+        blob_h = _np.zeros(o, _np.uint8)
+        desc = _np.zeros((k, words), _np.int32)
+        out_off, oo = [], 0
+        for j, (d, info) in enumerate(part):
+            blob_h[j * 768:(j + 1) * 768] = info['palette'].reshape(-1)
+            blob_h[stream_off[j]:stream_off[j] + info['stream_bytes']] = pngread.zlib_stream(d, info)
+            desc[j] = pngread.descriptor(info, stream_off[j], j * 768, oo)
+            out_off.append(oo)
+            oo += (info['height'] * info['width'] * 3 + 15) & ~15
+        with torch.cuda.device(dev):
+            blob = torch.from_numpy(blob_h).to(dev)
+            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
+            need = scratch_bytes(desc)
+            if need == 0:
+                raise _lib.CsmError("png_decode: %s" % L.csm_last_error().decode())
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+            info_h = (ctypes.c_int * 4)()
+            check(L.csm_png_decode(ptr(blob), i64(blob.numel()), desc.ctypes.data_as(c_desc), i32(k), ptr(pixels), i64(oo),
+                                   ptr(scratch), info_h, stream_ptr(dev)), "png_decode")
+        rounds.append((int(info_h[0]), int(info_h[1])))
+        for j, (_, info) in enumerate(part):
+            H, W = info['height'], info['width']
+            out.append(pixels[out_off[j]:out_off[j] + H * W * 3].view(H, W, 3))
+    if stats is not None:
+        stats['rounds'] = rounds
+    return out[0] if single else out
+
+
 # ---- PNG of device images (csrc/png.hip + pngcode.py; utils.io_utils.imwrite, the mask PNGs, video.write_apng) -------------
 PNG_SCRATCH_BYTES = 64 << 20           # images are encoded in chunks whose scratch stays below this (one image is always taken)
 

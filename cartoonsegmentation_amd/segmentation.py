@@ -168,7 +168,7 @@ class AnimeInsSeg:
         self.refine_method = None
         self.refine_batch = int(os.environ.get('CSM_REFINE_BATCH', '16'))   # instances per ISNet run when frames are batched
         self.det_batch = max(1, int(os.environ.get('CSM_DET_BATCH', '16')))  # frames per detector run (longer lists are chunked)
-        self.device_decode = os.environ.get('CSM_DEVICE_DECODE', '0') == '1'  # path inputs: baseline JPEGs are decoded on the device
+        self.device_decode = os.environ.get('CSM_DEVICE_DECODE', '0') == '1'  # path inputs: baseline JPEG and 8-bit PNG files are decoded on the device
         self.set_refine_method(**(refine_kwargs or {'refine_method': 'none'}))
 
     # ---- configuration (reference :395-399, :623-636, :704-708) --------------------------------
@@ -278,7 +278,8 @@ class AnimeInsSeg:
 
     def _load(self, imgs):
         """the path entries of `imgs` as images: imread (host, PIL), or with device_decode imread_device_many, one call per det_batch
-        chunk (baseline JPEGs are then decoded on the device; every other file still goes through imread)"""
+        chunk (baseline JPEG and 8-bit PNG files are then decoded on the device; every other file still goes
+        through imread)"""
         from utils.io_utils import imread, imread_device_many
         if not self.device_decode:
             return [imread(im) if isinstance(im, str) else im for im in imgs]

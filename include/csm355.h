@@ -26,7 +26,7 @@ extern "C" {
 #define CSM_ERR_ARG 1
 #define CSM_ERR_HIP 2
 #define CSM_ERR_NAN 3
-#define CSM_ERR_DATA 4   /* corrupt input data (csm_jpeg_decode) */
+#define CSM_ERR_DATA 4   /* corrupt input data (csm_jpeg_decode, csm_png_decode) */
 
 /* thread-local message of the last non-zero status */
 const char *csm_last_error(void);
@@ -564,6 +564,28 @@ int csm_jpeg_decode_subseq_bytes(void);
 int csm_jpeg_decode_desc_words(void);
 int csm_jpeg_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
                     void *scratch, int *info_host, void *stream);
+
+/* PNG files to uint8 B, G, R pixels (pngdec.hip; contract DESIGN.md §4.9, restated in tests/pngdec_restatement.py: the result
+ * equals utils.io_utils.imread on every byte).  The host parses the chunks (cartoonsegmentation_amd/pngread.py) and hands over one
+ * blob of device bytes and one descriptor per file; files of different sizes and colour types share a call.  8 bits per sample,
+ * colour types 0, 2, 3, 4, 6, not interlaced; alpha is dropped, a palette is looked up.
+ * desc_host: host int32 [n][csm_png_decode_desc_words() = 12]: [0] H, [1] W, [2] colour type, [3] [4] offset (a multiple of 16) and
+ *   length of the file's zlib stream (the concatenated IDAT payloads, header and Adler-32 trailer included) in the blob, whose bytes
+ *   reach to the stream's end rounded up to 16, [5] offset (a multiple of 16) of 768 palette bytes R, G, B in the blob (read for
+ *   colour type 3 only; any valid offset otherwise), [6] 0, [7] [8] the byte offset of the file's pixels in out
+ *   (low 31 bits, the bits above; a multiple of 4), the rest 0.  H * (1 + W * bytes per pixel) < 2^31.
+ * out: u8, file i at its offset as [H][W][3].  blob, out and scratch are 16-byte aligned.
+ * scratch: csm_png_decode_scratch_bytes(desc_host, n) device bytes (0 for invalid descriptors): per raw byte (scanlines with their
+ *   filter bytes) 1 B of literals, 4 B of source positions and 8/3 B of match records, plus 8 B per 4096 raw bytes and 200 B per file.
+ * csm_png_decode: info_host (may be NULL) receives [0] the pointer-doubling rounds launched, [1] the rounds that did work.  The call
+ *   SYNCHRONISES the stream once, at the end (one error word per file, bits as in csrc/csm_inflate.h).  Returns CSM_ERR_DATA for a
+ *   corrupt stream (invalid codes, distances or sizes, an Adler-32 that is not the one in the four bytes behind the deflate data, a filter type above 4; bytes behind that
+ *   trailer are ignored, as zlib ignores them); whatever the data, no read or
+ *   store leaves the file's own ranges.  No kernel waits on another workgroup; the output is deterministic. */
+size_t csm_png_decode_scratch_bytes(const int32_t *desc_host, int n);
+int csm_png_decode_desc_words(void);
+int csm_png_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
+                   void *scratch, int *info_host, void *stream);
 
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW

@@ -30,19 +30,25 @@ def imread(path):
         return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
 
 
-def imread_device_many(paths, device=None):
+def imread_device_many(paths, device=None, stats=None):
     """imread for a list of paths with the pixels on the device: a list of uint8 BGR [H,W,3] tensors.  A .jpg / .jpeg file that the
     device decoder takes (cartoonsegmentation_amd.jpegcode.probe: baseline, Huffman, grey or Y Cb Cr at 4:4:4 / 4:2:2 / 4:2:0) and
     whose EXIF orientation is 1 or absent is decoded on the MI355X by ops.jpeg_decode, all such files in one call: only the file's
-    bytes are uploaded.  Every other file (PNG, BMP, progressive or rotated JPEG, ...) goes through imread and an upload.  The
-    device decode follows the contract of DESIGN.md §4.8."""
+    bytes are uploaded.  A .png file that cartoonsegmentation_amd.pngread.probe accepts (8 bits per sample; grey, RGB, palette,
+    grey + alpha or RGBA; not interlaced, not animated, no orientation) is decoded by ops.png_decode, again all such files in one
+    call.  Every other file (BMP, progressive or rotated JPEG, 16-bit or interlaced PNG, ...) goes through imread and an upload.
+    The device decodes follow the contracts of DESIGN.md §4.8 (JPEG) and §4.9 (PNG: equal to imread on every byte).  `stats` (a
+    dict) receives 'jpeg', 'png' and 'host': the indices of the paths that took each route."""
     import torch
-    from cartoonsegmentation_amd import jpegcode, ops
+    from cartoonsegmentation_amd import jpegcode, ops, pngread
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     out = [None] * len(paths)
     idx, datas, infos = [], [], []
+    pidx, pdatas, pinfos = [], [], []
+    host = []
     for i, path in enumerate(paths):
-        if Path(str(path)).suffix.lower() in ('.jpg', '.jpeg'):
+        suffix = Path(str(path)).suffix.lower()
+        if suffix in ('.jpg', '.jpeg'):
             with open(path, 'rb') as f:
                 data = f.read()
             try:
@@ -52,10 +58,26 @@ def imread_device_many(paths, device=None):
             if info is not None and info['orientation'] in (None, 1):
                 idx.append(i); datas.append(data); infos.append(info)
                 continue
+        elif suffix == '.png':
+            with open(path, 'rb') as f:
+                data = f.read()
+            try:
+                info = pngread.probe(data)
+            except pngread.Unsupported:
+                info = None
+            if info is not None:
+                pidx.append(i); pdatas.append(data); pinfos.append(info)
+                continue
+        host.append(i)
         out[i] = torch.from_numpy(imread(path)).to(dev)
     if datas:
         for i, t in zip(idx, ops.jpeg_decode(datas, dev, _infos=infos)):
             out[i] = t
+    if pdatas:
+        for i, t in zip(pidx, ops.png_decode(pdatas, dev, _infos=pinfos)):
+            out[i] = t
+    if stats is not None:
+        stats.update(jpeg=idx, png=pidx, host=host)
     return out
 
 
