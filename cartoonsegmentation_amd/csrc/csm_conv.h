@@ -1,4 +1,5 @@
-// csm_conv.h -- device / host helpers shared by the convolution translation units of libcsm355 (nets.hip, wino.hip):
+// csm_conv.h -- device / host helpers shared by the convolution translation units of libcsm355 (nets.hip, conv_*.hip, netops.hip,
+// wino.hip, wino4.hip, grouped.hip):
 // scalar math of the numerical contract, NHWC views, the conv argument block, XCD-aware tile order, LDS-DMA.
 #pragma once
 #include "csm_common.h"

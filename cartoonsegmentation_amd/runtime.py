@@ -8,6 +8,23 @@ from . import _lib
 from ._lib import check, stream_ptr
 
 
+class _ConvCfgDesc(ctypes.Structure):      # csm_conv_cfg_desc (include/csm355.h)
+    _fields_ = [("id", ctypes.c_int32), ("bn", ctypes.c_int32), ("tune_pos", ctypes.c_int32), ("name", ctypes.c_char_p),
+                ("family", ctypes.c_char_p)]
+
+
+def conv_cfg_table():
+    """the conv tile configurations of libcsm355, one dict per id: id, name, family ('MFMA', 'DMA', 'PATCH', 'DMA_P', 'PATCH_P', 'WS',
+    'NARROW'), bn (output channels per tile), tune_pos (position in the autotuner's candidate order, -1 = never timed).  Host only."""
+    L = _lib.load()
+    table = []
+    for cfg in range(L.csm_debug_conv_cfg_count()):
+        d = _ConvCfgDesc()
+        check(L.csm_debug_conv_cfg_info(ctypes.c_int(cfg), ctypes.byref(d)), "conv_cfg_info(%d)" % cfg)
+        table.append({'id': d.id, 'name': d.name.decode(), 'family': d.family.decode(), 'bn': d.bn, 'tune_pos': d.tune_pos})
+    return table
+
+
 class CompiledProgram:
     """weights + workspace resident in HBM; run() enqueues the whole net on the current stream
     (no allocation, no host sync -> capturable in a hipGraph via torch.cuda.graph; the first run() tunes the conv tiles)."""

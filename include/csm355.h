@@ -240,7 +240,7 @@ typedef struct csm_tensor_desc {
 } csm_tensor_desc;
 
 /* Winograd contract (csm_op.flags & CSM_CONV_FLAG_WINOGRAD; restated in oracle/nets_oracle.c::orc_conv_wino, executed by
- * csrc/nets.hip::k_conv_wino): F(2x2, 3x3) with the transform matrices of Lavin & Gray (0, +-1, +-1/2 only).
+ * csrc/wino.hip::k_conv_wino): F(2x2, 3x3) with the transform matrices of Lavin & Gray (0, +-1, +-1/2 only).
  *   U[f = 4i + j][co][c] = fp32(G g G^T) evaluated in double, rows first: r0 = g0, r1 = ((g0 + g1) + g2) / 2, r2 = ((g0 - g1) + g2) / 2,
  *                          r3 = g2, then the same over the columns;
  *   V = B^T d B on the 4 x 4 input window d (origin (2 ty - 1, 2 tx - 1), zeros outside): t0 = d0 - d2, t1 = d1 + d2, t2 = d2 - d1,
@@ -300,7 +300,8 @@ typedef struct csm_op {
                                 CSM_CONV_FLAG_WINOGRAD4: optional (-1 = none) contiguous tensor of >= n * ceil(h/4) * ceil(w/4) * 24 * cout
                                 floats; with it the library may run launches of few block tiles in a row-split execution form of
                                 the same arithmetic (speed only: same bits) */
-    int32_t tile;            /* CONV: 0 = built-in tile rule; low 6 bits k > 0 = tile configuration k-1, bit 6 (64) = split-K runs
+    int32_t tile;            /* CONV: 0 = built-in tile rule; low 6 bits k > 0 = tile configuration k-1 (an id of the table in
+                                csrc/csm_convcfg.h, listed by csm_debug_conv_cfg_info), bit 6 (64) = split-K runs
                                 walked serially by one block instead of ksplit blocks + reduce, bit 7 (128) = mixed-tile launch (the
                                 configuration's tiles cover whole rounds of the grid, 64 x 64 tiles the remaining rows).  Speed only:
                                 every configuration and every launch form produces the same bits; filled in by csm_conv_autotune */
@@ -328,6 +329,21 @@ int csm_debug_force_splitk_serial(int mode);
 /* Measurement aid (not stable ABI): bit 0 = the autotuner may choose mixed-tile launches (default on); bit 1 = N-grouped tile order
  * (layers whose weights exceed an XCD's L2) OFF (default on).  Speed only. */
 int csm_debug_conv_tuner_options(int options);
+/* Test / tooling aid (not stable ABI, host only: no device is touched): the table of conv tile configurations.  csm_debug_conv_cfg_info
+ * fills `info` for id cfg in [0, csm_debug_conv_cfg_count()) -- the strings are static -- and returns CSM_ERR_ARG for any other id.
+ * csm_debug_conv_resolve_cfg: the id csm_run_program would launch for CONV `op` (not a stem / Winograd / grouped one) carrying
+ * configuration `cfg`, with the input and output views at their offsets from a NULL base (alignment follows the offsets; the weights
+ * likewise): a configuration whose kernel family cannot run the layer falls back.  Returns the id, or a negative status. */
+typedef struct csm_conv_cfg_desc {
+    int32_t id;
+    int32_t bn;              /* output channels per tile */
+    int32_t tune_pos;        /* position in csm_conv_autotune's candidate order; -1 = never timed */
+    const char *name;        /* e.g. "D128x64" */
+    const char *family;      /* kernel family: "MFMA", "DMA", "PATCH", "DMA_P", "PATCH_P", "WS" or "NARROW" */
+} csm_conv_cfg_desc;
+int csm_debug_conv_cfg_count(void);
+int csm_debug_conv_cfg_info(int cfg, csm_conv_cfg_desc *info);
+int csm_debug_conv_resolve_cfg(int cfg, const csm_op *op, const csm_tensor_desc *in_desc, const csm_tensor_desc *out_desc);
 /* Test aid (not stable ABI): bit 0 = CSM_OP_ATTENTION gathers the relative position bias from the table in global memory even when the
  * tile pair's window of the table fits the LDS budget (the path token grids wider than ~340 take).  Same results at the op's tolerance. */
 int csm_debug_attention_options(int options);

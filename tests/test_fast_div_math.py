@@ -1,5 +1,5 @@
 """The LDS-DMA conv kernels turn an output row m into (sample, oy, ox) with two divisions by run-time constants done as
-q = (mulhi(n, mul) + n) >> shr,  shr = ceil(log2 d),  mul = floor(2^32 (2^shr - d) / d) + 1     (csrc/nets.hip: fast_div / set_fast_div).
+q = (mulhi(n, mul) + n) >> shr,  shr = ceil(log2 d),  mul = floor(2^32 (2^shr - d) / d) + 1     (csrc/csm_conv.h: fast_div / set_fast_div).
 Exact for every dividend below 2^31 (the kernels' rows are below that: views < 2 GiB) -- checked here in numpy for divisors of every
 size, including the ho * wo and wo of the three nets; the sum mulhi + n stays below 2^32 (no carry lost in the 32-bit add)."""
 import numpy as np

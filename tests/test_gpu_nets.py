@@ -152,7 +152,7 @@ def test_full_size_all_tile_configurations_agree_bitwise(layer):
     k_conv_mfma, LDS-DMA k_conv_dma) must produce identical bits -- they share nothing but the fmaf-chain contract -- and one
     sampled output row block is checked against the chain evaluated in numpy float32."""
     from cartoonsegmentation_amd import _lib
-    from cartoonsegmentation_amd.runtime import CompiledProgram
+    from cartoonsegmentation_amd.runtime import CompiledProgram, conv_cfg_table
     n, h, w, cin, cout, k, stride, dil, groups = layer
     p = Program("full")
     p.winograd = False          # this test is about the DIRECT kernels' tile configurations (the Winograd layers have one kernel: test_gpu_winograd.py)
@@ -174,7 +174,7 @@ def test_full_size_all_tile_configurations_agree_bitwise(layer):
     L = _lib.load()
     ref, names = None, {}
     try:
-        for cfg in list(range(28)) + list(range(38, 53)):       # 38..49: the persistent-block kernels (fall back when K is split / not a 3x3)
+        for cfg in [c['id'] for c in conv_cfg_table()]:         # (the persistent-block and patch kernels fall back when K is split / not a 3x3)
             L.csm_debug_force_conv_cfg(cfg)
             cp.run()
             out = cp.read_view(y).cpu().numpy()
@@ -215,18 +215,15 @@ def test_full_size_all_tile_configurations_agree_bitwise(layer):
             assert np.array_equal(tot, ref[0, oy, ox]), "fmaf chain mismatch at (%d,%d): %g" % (oy, ox, np.abs(tot - ref[0, oy, ox]).max())
 
 
-# LDS-DMA tile configurations (include/csm355.h `tile`): plain 6-12 / 14-17 / 28-37, 3x3 patch 18-27 / 36, persistent 38-50, weights-stationary 51-52
-DMA_CFGS = [c for c in range(6, 53) if c != 13]
-
-
 def test_dma_kernels_repeated_runs_are_bitwise_stable():
     """stress test for the barrier / LDS hazard class (a stage refilled by DMA while a fragment read of it is still in flight shows as a
     few wrong values in 10^7, once in many runs): every LDS-DMA tile configuration x the eight BASELINE-size layers x both split-K
     executions, 20 repetitions each, every repetition compared bitwise with the first run of configuration 6 ON THE DEVICE (one host
     read per layer).  tools/check_isa_barriers.py is the static half of this check."""
     from cartoonsegmentation_amd import _lib
-    from cartoonsegmentation_amd.runtime import CompiledProgram
+    from cartoonsegmentation_amd.runtime import CompiledProgram, conv_cfg_table
     L = _lib.load()
+    DMA_CFGS = [c['id'] for c in conv_cfg_table() if c['family'] not in ('MFMA', 'NARROW')]      # every LDS-DMA family: plain, patch, persistent, weights-stationary
     reps = int(os.environ.get("CSM_STRESS_REPS", "20"))
     try:
         for layer in FULL_SIZE_LAYERS:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """every distinct conv layer of a net (RTMDet n=8 by default; argv: rtmdet|leres|isnet [batch]) as a one-op program: the persistent tile
-configurations (38..49, serial split-K forced) against configuration 6 with parallel split-K, bit for bit.
+configurations (the DMA_P, PATCH_P and WS families; serial split-K forced) against configuration 6 with parallel split-K, bit for bit.
 REPS=<n> repeats every configuration n times (rare races), ONLY3x3=1 keeps the stride-1 3x3 layers on maps of 40 px and more"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,7 +8,7 @@ os.environ["CSM_AUTOTUNE"] = "0"
 import numpy as np, torch
 from cartoonsegmentation_amd import nets, _lib
 from cartoonsegmentation_amd.program import Program
-from cartoonsegmentation_amd.runtime import CompiledProgram
+from cartoonsegmentation_amd.runtime import CompiledProgram, conv_cfg_table
 from cartoonsegmentation_amd.weights import SynthWeights
 which = sys.argv[1] if len(sys.argv) > 1 else 'rtmdet'
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 8
@@ -19,6 +19,7 @@ elif which == 'leres':
 else:
     prog = nets.build_isnet(SynthWeights('isnet.'), 2 * B, 720, 720)
 L = _lib.load()
+PERSISTENT = [c['id'] for c in conv_cfg_table() if c['family'] in ('DMA_P', 'PATCH_P', 'WS')]
 seen = set()
 bad = 0
 for o in prog.ops:
@@ -44,7 +45,7 @@ for o in prog.ops:
         return cp.read_view(y).clone()
     ref = run(6, 0)
     res = []
-    for cfg in range(38, 53):
+    for cfg in PERSISTENT:
         out = run(cfg, 1)
         for _ in range(int(os.environ.get('REPS', '1')) - 1):
             o2 = run(cfg, 1)

@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from cartoonsegmentation_amd.program import Program
-from cartoonsegmentation_amd.runtime import CompiledProgram
+from cartoonsegmentation_amd.runtime import CompiledProgram, conv_cfg_table
 
 # (mult, n, h, w, cin, cout, k, stride, dil, groups)   multiplicities ~ per-frame counts from tools/layer_profile.py
 LAYERS = [
@@ -43,7 +43,7 @@ def main():
         from cartoonsegmentation_amd import _lib
         L = _lib.load()
         per = []
-        for cfg in ([-1] + (list(range(28)) if SWEEP else [])):
+        for cfg in ([-1] + ([c['id'] for c in conv_cfg_table()] if SWEEP else [])):
             L.csm_debug_force_conv_cfg(cfg)
             cp.run()
             per.append(min(cp.profile()[0] for _ in range(4)))
@@ -53,6 +53,8 @@ def main():
         rows.append((mult * ms, mult, ms, fl, "%dx%dx%dx%d->%d k%d s%d d%d g%d S%d" % (n, y.h, y.w, cin, cout, k, s, d, g, p.ops[0]['ksplit']), per))
         tot_ms += mult * ms; tot_fl += mult * fl
         best_ms += mult * min(per)
+    if SWEEP:
+        print("sweep columns:", " ".join("%d=%s" % (c['id'], c['name']) for c in conv_cfg_table()))
     for tm, mult, ms, fl, desc, per in sorted(rows, key=lambda r: -r[0]):
         print("%7.3f ms = x%-2d %7.1f us  %6.1f TF/s  %-36s %s" % (tm, mult, ms * 1e3, fl / ms / 1e9, desc,
               " ".join("%5.0f" % (fl / t / 1e9) for t in per[1:])))
