@@ -7,6 +7,7 @@
 //   * frame tail  : cv2.getRectSubPix + cv2.resize(INTER_LINEAR) (kenburns_effect.py:1069-1070)
 #include "csm_common.h"
 #include "csm_resample.h"
+#include "csm_glue.h"
 
 namespace {
 
@@ -14,15 +15,6 @@ using csmimg::cv_src;
 using csmimg::cv_lin_u8;
 using csmimg::cv_lin_f32;
 
-// INTER_AREA when up-sampling: linear taps with "area" fractions (resize.cpp, area_mode branch)
-__device__ __forceinline__ void cv_src_area(int d, int in_size, double scale, int &i0, int &i1, float &f) {
-    int sx = (int)floor(d * scale);
-    float fx = (float)((d + 1) - (sx + 1) * (1.0 / scale));
-    fx = fx <= 0.0f ? 0.0f : fx - floorf(fx);
-    if (sx < 0) { fx = 0.0f; sx = 0; }
-    if (sx >= in_size - 1) { fx = 0.0f; sx = in_size - 1; }
-    i0 = sx; i1 = min(sx + 1, in_size - 1); f = fx;
-}
 
 struct Norm3 { float mean[3], stdv[3]; };
 
@@ -50,14 +42,7 @@ __global__ __launch_bounds__(256) void k_leres_quantize(const float *__restrict_
                                                          uint8_t *__restrict__ out) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    float mn = mnmx[0], mx = mnmx[1];
-    float o = 0.0f;
-    if ((double)(mx - mn) > 2.220446049250313e-16) o = 65535.0f * (d[i] - mn) / (mx - mn);
-    uint16_t u16 = (uint16_t)o;
-    float s = (float)u16 * (float)(255.0 / 65535.0);
-    int v = (int)rintf(fabsf(s));
-    v = v > 255 ? 255 : v;
-    out[i] = (uint8_t)(255 - v);
+    out[i] = csmglue::leres_quantize_px(d[i], mnmx[0], mnmx[1]);
 }
 
 // u8 [h,w] -> fp32 [H,W] with cv2.resize: INTER_AREA when enlarging (linear taps, area fractions), identity if same size
@@ -65,14 +50,7 @@ __global__ __launch_bounds__(256) void k_resize_u8_to_f32(const uint8_t *__restr
                                                            float *__restrict__ out) {
     const int y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x;
     if (x >= W) return;
-    int q;
-    if (h == H && w == W) q = src[(int64_t)y * w + x];
-    else {
-        int y0, y1, x0, x1; float fy, fx;
-        cv_src_area(y, h, (double)h / H, y0, y1, fy); cv_src_area(x, w, (double)w / W, x0, x1, fx);
-        q = cv_lin_u8(src[(int64_t)y0 * w + x0], src[(int64_t)y0 * w + x1], src[(int64_t)y1 * w + x0], src[(int64_t)y1 * w + x1], fx, fy);
-    }
-    out[(int64_t)y * W + x] = (float)q;
+    out[(int64_t)y * W + x] = csmglue::resize_u8_to_f32_px(src, h, w, H, W, y, x);
 }
 
 // cv2.getRectSubPix(frame, (pw,ph), center) followed by cv2.resize(..., (W,H), INTER_LINEAR); u8 HWC 3 channels.
@@ -175,112 +153,56 @@ __global__ __launch_bounds__(256) void k_crop_resize_tile(const uint8_t *__restr
 }
 
 // ---- small fused reductions of the per-frame depth glue (replace ~25 torch kernels per frame; min/max are order-free) ---------
-__device__ __forceinline__ unsigned f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float ord2f(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+using csmglue::f2ord;
+using csmglue::ord2f;
 
 // out[0] = min, out[1] = max of x[0..n): 256 blocks write partial {min, max} pairs, one block folds them (min / max are
 // order-free).  A single-block version measured 150 us on a 1024^2 map -- one CU cannot pull 4 MB fast enough.
 __global__ __launch_bounds__(256) void k_minmax_partial(const float *__restrict__ x, int64_t n, float *__restrict__ part) {
-    __shared__ float smn[256], smx[256];
-    float mn = INFINITY, mx = -INFINITY;
-    const int64_t n4 = n >> 2;
-    const float4 *x4 = reinterpret_cast<const float4 *>(x);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        float4 v = x4[i];
-        mn = fminf(fminf(mn, v.x), fminf(v.y, fminf(v.z, v.w)));
-        mx = fmaxf(fmaxf(mx, v.x), fmaxf(v.y, fmaxf(v.z, v.w)));
-    }
-    if (blockIdx.x == 0) for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) { float v = x[i]; mn = fminf(mn, v); mx = fmaxf(mx, v); }
-    smn[threadIdx.x] = mn; smx[threadIdx.x] = mx;
-    __syncthreads();
-    for (int st = 128; st >= 1; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            smn[threadIdx.x] = fminf(smn[threadIdx.x], smn[threadIdx.x + st]);
-            smx[threadIdx.x] = fmaxf(smx[threadIdx.x], smx[threadIdx.x + st]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { part[2 * blockIdx.x] = smn[0]; part[2 * blockIdx.x + 1] = smx[0]; }
+    csmglue::minmax_partial_block(x, n, blockIdx.x, gridDim.x, part);
 }
 __global__ __launch_bounds__(256) void k_minmax_final(const float *__restrict__ part, int nparts, float *__restrict__ out) {
-    __shared__ float smn[256], smx[256];
-    float mn = INFINITY, mx = -INFINITY;
-    for (int i = threadIdx.x; i < nparts; i += 256) { mn = fminf(mn, part[2 * i]); mx = fmaxf(mx, part[2 * i + 1]); }
-    smn[threadIdx.x] = mn; smx[threadIdx.x] = mx;
-    __syncthreads();
-    for (int st = 128; st >= 1; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            smn[threadIdx.x] = fminf(smn[threadIdx.x], smn[threadIdx.x + st]);
-            smx[threadIdx.x] = fmaxf(smx[threadIdx.x], smx[threadIdx.x + st]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out[0] = smn[0]; out[1] = smx[0]; }
+    csmglue::minmax_final_block(part, nparts, out);
 }
 
 // leres/__init__.py:143-145 `depth[depth == 0] = depth[depth > 0].min()`: pass 1 finds the smallest positive value (as ordered
 // uint, atomicMin) and whether a zero exists; pass 2 rewrites only if both hold.  st[0] = ordered min positive, st[1] = zero seen.
 __global__ __launch_bounds__(256) void k_minpos_scan(const float *__restrict__ x, int64_t n, unsigned *__restrict__ st) {
-    __shared__ unsigned smn[256]; __shared__ int sz[256];
     unsigned mn = 0xffffffffu; int z = 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float v = x[i];
-        if (v > 0.0f) mn = min(mn, __float_as_uint(v));      // positive floats order like their bit patterns
-        z |= v == 0.0f;
-    }
-    smn[threadIdx.x] = mn; sz[threadIdx.x] = z;
-    __syncthreads();
-    for (int s2 = 128; s2 >= 1; s2 >>= 1) {
-        if ((int)threadIdx.x < s2) { smn[threadIdx.x] = min(smn[threadIdx.x], smn[threadIdx.x + s2]); sz[threadIdx.x] |= sz[threadIdx.x + s2]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { atomicMin(&st[0], smn[0]); if (sz[0]) atomicOr(&st[1], 1u); }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) csmglue::minpos_acc(x[i], mn, z);
+    csmglue::minpos_fold_block(mn, z);
+    if (threadIdx.x == 0) { atomicMin(&st[0], mn); if (z) atomicOr(&st[1], 1u); }
 }
 __global__ __launch_bounds__(256) void k_minpos_apply(float *__restrict__ x, int64_t n, const unsigned *__restrict__ st) {
-    if (st[1] == 0u || st[0] == 0xffffffffu) return;         // no zero, or nothing positive: unchanged
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && x[i] == 0.0f) x[i] = __uint_as_float(st[0]);
+    if (i < n) csmglue::minpos_apply_px(x, i, st[0], st[1] != 0u);         // no zero, or nothing positive: unchanged
 }
 
 // kenburns_effect.py:928 `disparity / disparity.max() * baseline` (two roundings, like torch) with the maximum read on the device
 __global__ __launch_bounds__(256) void k_normalise(const float *__restrict__ x, int64_t n, const float *__restrict__ minmax, float scale,
                                                     float *__restrict__ out, float *__restrict__ norm_max) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (x[i] / minmax[1]) * scale;
-    if (i == 0 && norm_max) norm_max[0] = (minmax[1] / minmax[1]) * scale;     // = max of `out` (the map is monotonic)
+    if (i < n) out[i] = csmglue::normalise_px(x[i], minmax[1], scale);
+    if (i == 0 && norm_max) norm_max[0] = csmglue::normalise_px(minmax[1], minmax[1], scale);     // = max of `out` (the map is monotonic)
 }
 
 // cv2.minMaxLoc(depth[y0:y1, x0:x1]) (kenburns_effect.py:935): value and FIRST row-major position of the minimum and of the
 // maximum.  Keys = (ordered value << 32) | index (min) and (ordered value << 32) | ~index (max) through 64-bit atomics.
 __global__ __launch_bounds__(256) void k_crop_minmaxloc(const float *__restrict__ d, int W, int y0, int x0, int ch, int cw,
                                                          unsigned long long *__restrict__ keys) {
-    __shared__ unsigned long long kmn[256], kmx[256];
     unsigned long long mn = ~0ull, mx = 0ull;
     const int64_t n = (int64_t)ch * cw;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         int y = (int)(i / cw), x = (int)(i - (int64_t)y * cw);
-        unsigned o = f2ord(d[(int64_t)(y0 + y) * W + x0 + x]);
-        unsigned long long a = ((unsigned long long)o << 32) | (unsigned)i, b = ((unsigned long long)o << 32) | (unsigned)(~(unsigned)i);
-        mn = a < mn ? a : mn; mx = b > mx ? b : mx;
+        csmglue::crop_keys_acc(d[(int64_t)(y0 + y) * W + x0 + x], (unsigned)i, mn, mx);
     }
-    kmn[threadIdx.x] = mn; kmx[threadIdx.x] = mx;
-    __syncthreads();
-    for (int s2 = 128; s2 >= 1; s2 >>= 1) {
-        if ((int)threadIdx.x < s2) {
-            kmn[threadIdx.x] = kmn[threadIdx.x + s2] < kmn[threadIdx.x] ? kmn[threadIdx.x + s2] : kmn[threadIdx.x];
-            kmx[threadIdx.x] = kmx[threadIdx.x + s2] > kmx[threadIdx.x] ? kmx[threadIdx.x + s2] : kmx[threadIdx.x];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { atomicMin(&keys[0], kmn[0]); atomicMax(&keys[1], kmx[0]); }
+    csmglue::crop_keys_fold_block(mn, mx);
+    if (threadIdx.x == 0) { atomicMin(&keys[0], mn); atomicMax(&keys[1], mx); }
 }
 // out[0..5] (float64) = {raw_min_normalised, raw_max_normalised, crop min, crop max, crop argmin, crop argmax}
 __global__ void k_stats_pack(const float *__restrict__ minmax_raw, float scale, const unsigned long long *__restrict__ keys,
                              double *__restrict__ out) {
-    out[0] = (double)((minmax_raw[0] / minmax_raw[1]) * scale);     // min / max of the normalised map: x -> (x/m)*s is monotonic
-    out[1] = (double)((minmax_raw[1] / minmax_raw[1]) * scale);
-    out[2] = (double)ord2f((unsigned)(keys[0] >> 32)); out[3] = (double)ord2f((unsigned)(keys[1] >> 32));
-    out[4] = (double)(unsigned)(keys[0] & 0xffffffffull); out[5] = (double)(unsigned)(~(unsigned)(keys[1] & 0xffffffffull));
+    csmglue::stats_pack(minmax_raw, scale, keys[0], keys[1], out);
 }
 
 }  // namespace
@@ -335,49 +257,12 @@ extern "C" int csm_resize_f32_linear(const float *src_hwc, int H, int W, int C, 
 // frame, k > 1).  [EXT: OpenCV 4.10 resize.cpp restated: source coordinate (d + 0.5) scale - 0.5, 8 taps sx-3..sx+4 with replicate
 // clamping per tap, interpolateLanczos4 coefficients in float -> short Q11 (cvRound), horizontal pass to int, vertical pass, result
 // (v + 2^21) >> 22 saturated.]
-__device__ __forceinline__ void lanczos4_q11(float x, int c[8]) {
-    const double s45 = 0.70710678118654752440084436210485;
-    const double cs[8][2] = {{1, 0}, {-s45, -s45}, {0, 1}, {s45, -s45}, {-1, 0}, {s45, s45}, {0, -1}, {-s45, s45}};
-    float coeffs[8], sum = 0.0f;
-    const double y0 = -(x + 3) * 3.14159265358979323846 * 0.25, s0 = sin(y0), c0 = cos(y0);
-    for (int i = 0; i < 8; ++i) {
-        const float y0_ = (x + 3 - i);
-        if (fabsf(y0_) >= 1e-6f) {
-            const double y = -y0_ * 3.14159265358979323846 * 0.25;
-            coeffs[i] = (float)((cs[i][0] * s0 + cs[i][1] * c0) / (y * y));
-        } else coeffs[i] = 1e30f;
-        sum += coeffs[i];
-    }
-    sum = 1.0f / sum;
-    for (int i = 0; i < 8; ++i) {
-        const float v = coeffs[i] * sum * 2048.0f;
-        int q = (int)rintf(v);
-        c[i] = q > 32767 ? 32767 : (q < -32768 ? -32768 : q);
-    }
-}
 
 __global__ __launch_bounds__(256) void k_resize_u8_lanczos4(const uint8_t *__restrict__ src, int h, int w, int H, int W,
                                                              float *__restrict__ out) {
     const int y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x;
     if (x >= W) return;
-    float fx = (float)((x + 0.5) * ((double)w / W) - 0.5), fy = (float)((y + 0.5) * ((double)h / H) - 0.5);
-    int sx = (int)floorf(fx), sy = (int)floorf(fy);
-    fx -= (float)sx; fy -= (float)sy;
-    int cx[8], cy[8];
-    lanczos4_q11(fx, cx); lanczos4_q11(fy, cy);
-    int acc = 0;
-    for (int j = 0; j < 8; ++j) {
-        int yy = sy - 3 + j; yy = yy < 0 ? 0 : (yy > h - 1 ? h - 1 : yy);
-        int row = 0;
-        for (int i = 0; i < 8; ++i) {
-            int xx = sx - 3 + i; xx = xx < 0 ? 0 : (xx > w - 1 ? w - 1 : xx);
-            row += (int)src[(int64_t)yy * w + xx] * cx[i];
-        }
-        acc += row * cy[j];
-    }
-    int v = (acc + (1 << 21)) >> 22;
-    v = v < 0 ? 0 : (v > 255 ? 255 : v);
-    out[(int64_t)y * W + x] = (float)v;
+    out[(int64_t)y * W + x] = csmglue::resize_u8_lanczos4_px(src, h, w, H, W, y, x);
 }
 
 extern "C" int csm_resize_u8_lanczos4_to_f32(const uint8_t *src, int h, int w, int H, int W, float *out, void *stream) {
@@ -406,68 +291,19 @@ extern "C" int csm_leres_quantize(const float *depth, int64_t n, const float *mi
 // become val.  Skipped when the plane is empty (`plane.sum() == 0`).  scratch: H row maxima, H row flags, {val, apply}.
 __global__ __launch_bounds__(256) void k_adjust_rows(const float *__restrict__ disp, const uint8_t *__restrict__ mask, int W,
                                                        float *__restrict__ rowmax, float *__restrict__ rowflag) {
-    __shared__ float smax[256];
-    __shared__ int sflag[256];
-    const int r = blockIdx.x;
-    float mx = -INFINITY; int fl = 0;           // bit 0: a positive entry, bit 1: a non-zero entry
-    for (int x = threadIdx.x; x < W; x += 256) {
-        float p = disp[(int64_t)r * W + x] * (mask[(int64_t)r * W + x] ? 1.0f : 0.0f);
-        mx = fmaxf(mx, p);
-        fl |= (p > 0.0f ? 1 : 0) | (p != 0.0f ? 2 : 0);
-    }
-    smax[threadIdx.x] = mx; sflag[threadIdx.x] = fl;
-    __syncthreads();
-    for (int st = 128; st >= 1; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + st]);
-            sflag[threadIdx.x] |= sflag[threadIdx.x + st];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { rowmax[r] = smax[0]; rowflag[r] = (float)sflag[0]; }
+    csmglue::adjust_rows_block(disp, mask, W, blockIdx.x, rowmax, rowflag);
 }
 
 __global__ __launch_bounds__(256) void k_adjust_pick(const float *__restrict__ rowmax, const float *__restrict__ rowflag, int H,
                                                        float *__restrict__ out2) {
-    __shared__ int stop[256], sbot[256], snz[256];
-    __shared__ float smax[256];
-    int top = H, bot = -1, nz = 0;
-    for (int r = threadIdx.x; r < H; r += 256) {
-        int f = (int)rowflag[r];
-        if (f & 1) { top = min(top, r); bot = max(bot, r); }
-        nz |= f & 2;
-    }
-    stop[threadIdx.x] = top; sbot[threadIdx.x] = bot; snz[threadIdx.x] = nz;
-    __syncthreads();
-    for (int st = 128; st >= 1; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            stop[threadIdx.x] = min(stop[threadIdx.x], stop[threadIdx.x + st]);
-            sbot[threadIdx.x] = max(sbot[threadIdx.x], sbot[threadIdx.x + st]);
-            snz[threadIdx.x] |= snz[threadIdx.x + st];
-        }
-        __syncthreads();
-    }
-    top = stop[0]; bot = sbot[0]; nz = snz[0];
-    const bool apply = bot >= 0 && nz != 0;
-    const int r0 = apply ? (int)rint((double)top + (0.97 * (double)(bot - top))) : H;
-    float mx = -INFINITY;
-    for (int r = threadIdx.x; r < H; r += 256)
-        if (r >= r0) mx = fmaxf(mx, rowmax[r]);
-    smax[threadIdx.x] = mx;
-    __syncthreads();
-    for (int st = 128; st >= 1; st >>= 1) {
-        if ((int)threadIdx.x < st) smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + st]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out2[0] = smax[0]; out2[1] = apply ? 1.0f : 0.0f; }
+    csmglue::adjust_pick_block(rowmax, rowflag, H, out2);
 }
 
 __global__ __launch_bounds__(256) void k_adjust_apply(float *__restrict__ disp, const uint8_t *__restrict__ mask, int64_t n,
                                                         const float *__restrict__ out2) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || out2[1] == 0.0f) return;
-    const float m = mask[i] ? 1.0f : 0.0f;
-    disp[i] = ((1.0f - m) * disp[i]) + (m * out2[0]);          // kenburns_effect.py:78, literally
+    disp[i] = csmglue::adjust_apply_px(disp[i], mask[i], out2[0]);
 }
 
 extern "C" int csm_depth_adjust_instance(float *disp, const uint8_t *mask, int H, int W, float *scratch, void *stream) {
@@ -481,7 +317,7 @@ extern "C" int csm_depth_adjust_instance(float *disp, const uint8_t *mask, int H
 
 extern "C" int csm_minmax(const float *x, int64_t n, float *out2, float *scratch512, void *stream) {
     CSM_REQUIRE(x && out2 && scratch512 && n > 0 && !(((uintptr_t)x) & 15));
-    const int nparts = (int)(n >= (1 << 18) ? 256 : (n + 1023) / 1024 > 0 ? (n + 1023) / 1024 : 1);
+    const int nparts = csmglue::minmax_nparts(n);
     k_minmax_partial<<<nparts, 256, 0, (hipStream_t)stream>>>(x, n, scratch512);
     k_minmax_final<<<1, 256, 0, (hipStream_t)stream>>>(scratch512, nparts, out2);
     return csm::check_launch("k_minmax");
@@ -522,8 +358,7 @@ namespace {
 __global__ __launch_bounds__(256) void k_u8_hwc_to_f32_chw(const uint8_t *__restrict__ src, int64_t plane, float *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= plane) return;
-    const float s = (float)(1.0 / 255.0);
-    out[i] = (float)src[i * 3] * s; out[plane + i] = (float)src[i * 3 + 1] * s; out[2 * plane + i] = (float)src[i * 3 + 2] * s;
+    csmglue::u8_hwc_to_f32_chw_px(src, plane, i, out);
 }
 }  // namespace
 extern "C" int csm_u8_hwc_to_f32_chw(const uint8_t *src_hwc, int H, int W, float *out_chw, void *stream) {

@@ -14,6 +14,7 @@
 // Built with -ffp-contract=off: every fp32/fp64 operation rounds exactly once, as written, so
 // integer/decision results are bit-identical to oracle/warp_oracle.c.
 #include "warp_device.h"
+#include "csm_glue.h"
 
 namespace {
 using namespace csmwarp;
@@ -323,25 +324,7 @@ __global__ __launch_bounds__(kBlock) void k_fill_holes(const float *__restrict__
 }
 
 // spatial_filter 'laplacian' (models/utils.py:12-24): replicate pad + asymmetric 3x3
-__device__ __forceinline__ float laplacian_at(const float *__restrict__ I, int x, int y, int H, int W, float scale_div) {
-    int ym = y > 0 ? y - 1 : 0, yp = y < H - 1 ? y + 1 : H - 1;
-    int xm = x > 0 ? x - 1 : 0, xp = x < W - 1 ? x + 1 : W - 1;
-    float acc = 0.0f;
-    if (scale_div != 0.0f) {
-        acc += -1.0f * (I[(int64_t)ym * W + x] / scale_div);
-        acc += -1.0f * (I[(int64_t)ym * W + xp] / scale_div);
-        acc += -1.0f * (I[(int64_t)y * W + xm] / scale_div);
-        acc += 4.0f * (I[(int64_t)y * W + x] / scale_div);
-        acc += -1.0f * (I[(int64_t)yp * W + xm] / scale_div);
-    } else {
-        acc += -1.0f * I[(int64_t)ym * W + x];
-        acc += -1.0f * I[(int64_t)ym * W + xp];
-        acc += -1.0f * I[(int64_t)y * W + xm];
-        acc += 4.0f * I[(int64_t)y * W + x];
-        acc += -1.0f * I[(int64_t)yp * W + xm];
-    }
-    return acc;
-}
+using csmglue::laplacian_at;
 
 __global__ __launch_bounds__(kBlock) void k_laplacian(const float *__restrict__ in, float *__restrict__ out, int H,
                                                        int W) {
@@ -411,15 +394,8 @@ __global__ __launch_bounds__(kBlock) void k_disparity_to_points(const float *__r
     int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
-    const int64_t plane = (int64_t)H * W, o = (int64_t)y * W + x;
-    float d = (1.0f / (disp[o] + eps)) * fb;  // float / Tensor == reciprocal()*float in torch
-    float lap = laplacian_at(disp, x, y, H, W, disp_max_p[0]);
-    float v = fabsf(lap) < 0.03f ? 1.0f : 0.0f;
-    float hx = (x_start + (float)x) * invf, vy = (y_start + (float)y) * invf;
-    depth[o] = d; valid[o] = v;
-    float dv = d * v;
-    pts[o] = dv * hx; pts[plane + o] = dv * vy; pts[2 * plane + o] = dv;
-    unaltered[o] = d * hx; unaltered[plane + o] = d * vy; unaltered[2 * plane + o] = d;
+    csmglue::disparity_to_points_px([disp](int64_t i) { return disp[i]; }, disp[(int64_t)y * W + x], disp_max_p[0], x, y, H, W, fb, eps, invf,
+                                    x_start, y_start, depth, valid, pts, unaltered);
 }
 
 __global__ __launch_bounds__(kBlock) void k_process_shift(const float *__restrict__ pts, float *__restrict__ out,

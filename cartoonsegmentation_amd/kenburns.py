@@ -147,6 +147,14 @@ def _fill_zero_with_min_positive(depth):
     return depth
 
 
+def _instance_masks_u8(instances, device):
+    """the instance masks as one contiguous uint8 [n,H,W] device tensor (bool masks reinterpreted, other dtypes thresholded at 0)"""
+    mk = instances.masks if isinstance(instances.masks, torch.Tensor) else torch.as_tensor(instances.masks)
+    mk = mk.to(device)
+    mk = mk if mk.dtype in (torch.bool, torch.uint8) else (mk > 0)
+    return mk.contiguous().view(torch.uint8)
+
+
 def depth_adjustment_animesseg(instances, tenDisparity, tenImage, use_medium=False):
     """kenburns_effect.py:39-91: flatten every instance to the disparity at the bottom 3% of its rows"""
     assert tenDisparity.shape[0] == 1
@@ -165,10 +173,7 @@ def depth_adjustment_animesseg(instances, tenDisparity, tenImage, use_medium=Fal
         H, W = int(adj.shape[2]), int(adj.shape[3])
         adj = adj.clone() if not resized else adj.contiguous()
         scratch = torch.empty(2 * H + 2, dtype=torch.float32, device=adj.device)
-        mk = instances.masks if isinstance(instances.masks, torch.Tensor) else torch.as_tensor(instances.masks)
-        mk = mk.to(adj.device)
-        mk = mk if mk.dtype in (torch.bool, torch.uint8) else (mk > 0)
-        mk = mk.contiguous().view(torch.uint8)
+        mk = _instance_masks_u8(instances, adj.device)
         for i in range(mk.shape[0]):
             check(_lib.load().csm_depth_adjust_instance(ptr(adj), ptr(mk[i]), i32(H), i32(W), ptr(scratch), stream_ptr()), "depth_adjust")
     if resized:
@@ -485,17 +490,8 @@ class KenBurnsPipeline:
             check(L.csm_leres_input(ptr(im), i32(H), i32(W), i32(h), i32(w), ptr(x[bi]), stream_ptr()), "leres_input")
         y = torch.empty((nb, 1, h, w), dtype=torch.float32, device=self.device)
         self._leres_prog(h, w, nb, slot).run(x, y)
-        outs = []
-        for bi in range(nb):
-            yb = y[bi]
-            mnmx = torch.empty(2, dtype=torch.float32, device=self.device)
-            check(L.csm_minmax(ptr(yb), i64(h * w), ptr(mnmx), ptr(_mm_scratch(yb)), stream_ptr()), "minmax")
-            q = torch.empty((h, w), dtype=torch.uint8, device=self.device)
-            check(L.csm_leres_quantize(ptr(yb), i64(h * w), ptr(mnmx), ptr(q), stream_ptr()), "leres_quantize")
-            depth = torch.empty((1, 1, H, W), dtype=torch.float32, device=self.device)
-            self._leres_resize_back(q, h, w, H, W, depth)
-            outs.append(_fill_zero_with_min_positive(depth))
-        return outs
+        # min/max -> uint8 -> resize back (_leres_resize_back's two routes) -> zero fix of all nb samples: one native call
+        return ops.leres_post_batch(y, H, W)
 
     def _depth_est_leres(self, img_tensor, img_d):
         """img_d: uint8 BGR HWC device tensor -> 'depth' (inverse-depth like, 1..255) fp32 [1,1,H,W]"""
@@ -590,7 +586,8 @@ class KenBurnsPipeline:
 
     def generate_kenburns_configs(self, imgs, verbose: bool = False):
         """MI355X addition (the reference loops image by image, run_kenburns_batch.py:36-62): equally sized frames share one
-        batched detector run, shared ISNet refine batches and one batched LeReS run; the per-frame glue is unchanged."""
+        batched detector run, shared ISNet refine batches, one batched LeReS run and one native call for the per-frame depth glue
+        (_configs_batched: the bits of the per-frame path, one host read for all frames)."""
         with torch.no_grad():
             imgs_d = [self.animeinsseg._upload(im) for im in imgs]
             frames_d = [self._scaled_frame(t) for t in imgs_d]
@@ -630,7 +627,52 @@ class KenBurnsPipeline:
             else:
                 insts = seg()
                 coarse = depth_of(frames_d, 0)
+            if self._glue_batchable(frames_d, coarse, verbose):
+                return self._configs_batched(imgs, insts, coarse, frames_d)
             return [self._config_from(im, inst, c, verbose, frame_dev=f) for im, inst, c, f in zip(imgs, insts, coarse, frames_d)]
+
+    def _glue_batchable(self, frames_d, coarse, verbose):
+        """may the depth glue of these frames go through csm_frame_glue_batch?  Equal frame sizes, disparities at the frame size,
+        and none of the stages that only the per-frame path has (median adjustment, depth refinement, CRF, verbose stage images)"""
+        if verbose or self.cfg.depthest_use_medium or self.cfg.default_depth_refine or self.cfg.refine_crf:
+            return False
+        H, W = int(frames_d[0].shape[0]), int(frames_d[0].shape[1])
+        if H <= 256 or W <= 256:                                  # no [128:-128, 128:-128] crop: the per-frame path reports it
+            return False
+        return all(tuple(f.shape) == (H, W, 3) for f in frames_d) and \
+            all(c.dtype == torch.float32 and tuple(c.shape) == (1, 1, H, W) for c in coarse)
+
+    def _configs_batched(self, imgs, insts, coarse, frames_d):
+        """_config_from + _finish_config for equally sized frames: ONE native call (ops.frame_glue_batch) and ONE host read of the
+        [B, 6] stats instead of ~20 launches and one read per frame.  The config tensors are views of block-allocated [B, ...]
+        outputs with the shapes and contiguity of the per-frame path."""
+        H, W = int(frames_d[0].shape[0]), int(frames_d[0].shape[1])
+        cfgs, kept, masks = [], [], []
+        for im, inst, f in zip(imgs, insts, frames_d):
+            inst.resize(H, W)
+            self.cfg.int_height, self.cfg.int_width = H, W
+            cfgs.append(self.cfg.copy())
+            if tuple(f.shape) == tuple(im.shape):
+                kept.append(im)                                        # cfg.original_img_nparray: the caller's own array / tensor
+            else:
+                kept.append(f if isinstance(im, torch.Tensor) else f.cpu().numpy())
+            masks.append(None if inst.is_empty else _instance_masks_u8(inst, self.device))
+        g = ops.frame_glue_batch([f.contiguous() for f in frames_d], [c.contiguous() for c in coarse], masks, self.cfg.focal, self.cfg.baseline)
+        stats = g['stats'].tolist()                                    # the one host sync of this stage, for all frames
+        cw = W - 256
+        for k, cfg in enumerate(cfgs):
+            st = stats[k]
+            cfg['fltDispmin'], cfg['fltDispmax'] = st[0], st[1]
+            amin, amax = int(st[4]), int(st[5])
+            cfg['objDepthrange'] = (st[2], st[3], (amin % cw, amin // cw), (amax % cw, amax // cw))
+            img_tensor, disparity, depth = g['image'][k], g['disparity'][k], g['depth'][k]
+            cfg['tenRawImage'], cfg['tenRawDisparity'], cfg['tenRawDepth'] = img_tensor, disparity, depth
+            cfg['tenRawPoints'], cfg['tenRawUnaltered'] = g['points'][k].view(1, 3, -1), g['unaltered'][k].view(1, 3, -1)
+            cfg.inpainted_img = img_tensor.view(1, 3, -1)
+            cfg['tenInpaDisparity'], cfg['tenInpaDepth'] = disparity.view(1, 1, -1), depth.view(1, 1, -1)
+            cfg['tenInpaPoints'] = cfg['tenRawPoints']
+            cfg.instances, cfg.original_img_nparray = insts[k], kept[k]
+        return cfgs
 
     def _config_from(self, img, instances, coarse, verbose=False, frame_dev=None):
         """kenburns_effect.py:917-951 from the scaled frame on: instances.resize, depth glue, point cloud"""

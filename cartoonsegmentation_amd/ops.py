@@ -462,6 +462,64 @@ def image_tensor(img_hwc_u8):
     return out
 
 
+def _frame_block(B, n, dev, dtype=torch.float32):
+    """[B, stride] block for B frames of n elements each, stride = n rounded up to 4 elements: every frame's view starts 16-byte
+    aligned like a tensor of its own (csm_minmax and other float4 readers require it)"""
+    stride = (n + 3) & ~3
+    return torch.empty((B, stride), dtype=dtype, device=dev), stride
+
+
+def frame_glue_batch(frames, coarse, masks, fltFocal, fltBaseline, eps=0.00001):
+    """The per-frame depth glue of B equally sized frames in one native call (csm_frame_glue_batch): image_tensor, the depth
+    adjustment for each frame's instances, raw min/max, normalisation, disparity_to_points and the depth crop's minMaxLoc.
+    frames: B uint8 [H,W,3] device tensors; coarse: B float32 [1,1,H,W]; masks: B uint8 [n_k,H,W] tensors or None (no instance).
+    Returns per-frame VIEWS of block-allocated [B, ...] outputs, with the shapes the per-frame operators hand out, and the
+    [B, 6] float64 stats tensor (still on the device: the caller reads it once)."""
+    import ctypes
+    L = _lib.load()
+    B = len(frames)
+    H, W = int(frames[0].shape[0]), int(frames[0].shape[1])
+    dev, n = frames[0].device, H * W
+    for f, c, m in zip(frames, coarse, masks):
+        if not (f.is_cuda and f.dtype == torch.uint8 and tuple(f.shape) == (H, W, 3) and f.is_contiguous()):
+            raise _lib.CsmError("frame_glue_batch: equally sized contiguous uint8 HxWx3 device frames are required")
+        if not (c.is_cuda and c.dtype == torch.float32 and c.numel() == n and c.is_contiguous()):
+            raise _lib.CsmError("frame_glue_batch: every coarse disparity must be a contiguous float32 device map of the frame size")
+        if m is not None and not (m.is_cuda and m.dtype == torch.uint8 and tuple(m.shape[1:]) == (H, W) and m.is_contiguous()):
+            raise _lib.CsmError("frame_glue_batch: masks must be contiguous uint8 [n,H,W] device tensors")
+    img, s3 = _frame_block(B, 3 * n, dev)
+    pts, un = torch.empty_like(img), torch.empty_like(img)
+    disp, s1 = _frame_block(B, n, dev)
+    depth, valid = torch.empty_like(disp), torch.empty_like(disp)
+    nmax = torch.empty(B, dtype=torch.float32, device=dev)
+    stats = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    scratch = torch.empty(L.csm_frame_glue_scratch_bytes(i32(B), i32(H), i32(W)), dtype=torch.uint8, device=dev)
+    VP = ctypes.c_void_p * B
+    counts = [0 if m is None else int(m.shape[0]) for m in masks]
+    check(L.csm_frame_glue_batch(i32(B), i32(H), i32(W), VP(*[f.data_ptr() for f in frames]), VP(*[c.data_ptr() for c in coarse]),
+                                 VP(*[m.data_ptr() if k else None for m, k in zip(masks, counts)]), (ctypes.c_int * B)(*counts),
+                                 f64(fltFocal), f64(fltBaseline), f32(eps), ptr(img), ptr(disp), ptr(depth), ptr(valid), ptr(pts), ptr(un),
+                                 i64(s1), i64(s3), ptr(nmax), ptr(stats), ptr(scratch), stream_ptr()), "frame_glue_batch")
+    v1 = lambda t, k: t[k, :n].view(1, 1, H, W)
+    v3 = lambda t, k: t[k, :3 * n].view(1, 3, H, W)
+    return {'image': [v3(img, k) for k in range(B)], 'disparity': [v1(disp, k) for k in range(B)],
+            'depth': [v1(depth, k) for k in range(B)], 'valid': [v1(valid, k) for k in range(B)],
+            'points': [v3(pts, k) for k in range(B)], 'unaltered': [v3(un, k) for k in range(B)], 'nmax': nmax, 'stats': stats}
+
+
+def leres_post_batch(y, H, W):
+    """LeReS post-processing of the net outputs y [B,1,h,w] in one native call (csm_leres_post_batch): per sample min/max -> uint8
+    quantisation -> resize back to H x W -> zero fix.  Returns B views [1,1,H,W] of one block."""
+    L = _lib.load()
+    y = _dev(y, "y")
+    B, h, w = int(y.shape[0]), int(y.shape[-2]), int(y.shape[-1])
+    out, stride = _frame_block(B, H * W, y.device)
+    scratch = torch.empty(L.csm_leres_post_scratch_bytes(i32(B), i32(h), i32(w)), dtype=torch.uint8, device=y.device)
+    check(L.csm_leres_post_batch(ptr(y), i32(B), i32(h), i32(w), i32(H), i32(W), ptr(out), i64(stride), ptr(scratch), stream_ptr()),
+          "leres_post_batch")
+    return [out[k, :H * W].view(1, 1, H, W) for k in range(B)]
+
+
 def ctypes_ptr(t, offset_elems):
     """device pointer `offset_elems` elements into tensor t"""
     import ctypes

@@ -644,6 +644,30 @@ int csm_depth_range_stats(const float *minmax_raw_dev, float scale, const float 
  * (bool/uint8 [H,W]) take the maximum of disp*mask over the rows from round(top + 0.97 (bottom - top)) down; untouched when the
  * instance plane is empty.  scratch: 2*H + 2 floats (device).  No host sync. */
 int csm_depth_adjust_instance(float *disp, const uint8_t *mask, int H, int W, float *scratch, void *stream);
+/* The per-frame depth glue of B equally sized frames in ONE asynchronous call (no allocation, no synchronisation, no pointer
+ * table in device memory: frames_hwc / coarse / masks / n_inst are HOST arrays of B entries, read before the call returns and
+ * passed on by value in kernel arguments, 16 frames per launch).  Frame k gets exactly what the single-frame entry points give,
+ * bit for bit (both compile the expressions of csrc/csm_glue.h):
+ *   img_out       [B][stride3]  csm_u8_hwc_to_f32_chw of frames_hwc[k] (uint8 [H,W,3])
+ *   (scratch)                   a private copy of coarse[k] (float [H,W]) after csm_depth_adjust_instance for the n_inst[k] masks of
+ *                               masks[k] (uint8 / bool [n,H,W]) in instance order; n_inst[k] == 0: coarse[k] itself, masks[k] unused
+ *   disp_out      [B][stride1]  csm_normalise_disparity(raw, csm_minmax(raw), baseline); nmax_out [B] its norm_max_out
+ *   depth_out, valid_out [B][stride1], pts_out, unaltered_out [B][stride3]   csm_disparity_to_points(disp, nmax, focal, baseline, eps)
+ *   stats_out     [B][6] float64  csm_depth_range_stats of the crop depth[128:H-128, 128:W-128] (so H, W > 256)
+ * stride1 >= H*W and stride3 >= 3*H*W are the frame strides of the outputs in floats (a multiple of 4 keeps every frame 16-byte
+ * aligned).  scratch: csm_frame_glue_scratch_bytes(B, H, W) bytes, 16-byte aligned, not shared by calls that may run concurrently. */
+size_t csm_frame_glue_scratch_bytes(int B, int H, int W);
+int csm_frame_glue_batch(int B, int H, int W, const uint8_t *const *frames_hwc, const float *const *coarse,
+                         const uint8_t *const *masks, const int *n_inst, double focal, double baseline, float eps, float *img_out,
+                         float *disp_out, float *depth_out, float *valid_out, float *pts_out, float *unaltered_out, int64_t stride1,
+                         int64_t stride3, float *nmax_out, double *stats_out, void *scratch, void *stream);
+/* The LeReS post-processing of B equally sized net outputs y [B,h,w] in ONE asynchronous call: per sample csm_minmax ->
+ * csm_leres_quantize -> csm_resize_u8_to_f32 (h <= H; needs w <= W too) or csm_resize_u8_lanczos4_to_f32 (h > H) ->
+ * csm_fill_zero_min_positive, bit for bit.  depth_out [B][out_stride] floats, out_stride >= H*W.
+ * scratch: csm_leres_post_scratch_bytes(B, h, w) bytes, 8-byte aligned. */
+size_t csm_leres_post_scratch_bytes(int B, int h, int w);
+int csm_leres_post_batch(const float *y, int B, int h, int w, int H, int W, float *depth_out, int64_t out_stride, void *scratch,
+                         void *stream);
 /* kenburns_effect.py:572-575: cv2.resize(u8 depth, (W,H), INTER_AREA) (enlarging) -> float32 */
 int csm_resize_u8_to_f32(const uint8_t *src, int h, int w, int H, int W, float *out, void *stream);
 /* uint8 [H,W,3] -> float32 [3,H,W] * (1/255): the image tensor of kenburns_effect.py:878-880 (`permute(2,0,1)[None].float() * (1.0 / 255.0)`) */
