@@ -850,9 +850,13 @@ def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False
     is still encoded once; the file holds the reference's seq + seq[::-1][1:-1], 2n - 2 chunks.
 
     A path ending in .apng (any letter case) is written as a lossless animated PNG the same way (ops.png_streams,
-    video.write_apng; `quality` and `subsampling` do not apply)."""
+    video.write_apng; `quality` and `subsampling` do not apply).
+
+    A path ending in .gif (any letter case) is written as an animated GIF the same way: one 256-colour palette for the clip, an
+    ordered dither and the LZW coding on the device (ops.gif_quantize, ops.gif_streams), the container by video.write_gif;
+    `quality` and `subsampling` do not apply."""
     suffix = str(video_save_path).lower()
-    if suffix.endswith('.avi') or suffix.endswith('.apng'):
+    if suffix.endswith('.avi') or suffix.endswith('.apng') or suffix.endswith('.gif'):
         from . import video
         if isinstance(npy_frame_list, torch.Tensor):
             frames = npy_frame_list
@@ -864,6 +868,12 @@ def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False
             streams, W, H, colour_type = ops.png_streams(frames, bgr=True)
             order = video.playback_order(len(streams)) if playback else None
             video.write_apng(video_save_path, streams, W, H, colour_type, fps=25, order=order)
+            return
+        if suffix.endswith('.gif'):
+            indices, palette = ops.gif_quantize(frames, bgr=True)
+            streams, W, H = ops.gif_streams(indices)
+            order = video.playback_order(len(streams)) if playback else None
+            video.write_gif(video_save_path, streams, W, H, palette, fps=25, order=order)
             return
         jpegs = ops.jpeg_encode(frames, quality=quality, subsampling=subsampling)
         order = video.playback_order(len(jpegs)) if playback else None

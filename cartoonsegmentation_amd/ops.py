@@ -893,6 +893,114 @@ def png_encode(images, bgr=True):
     return [pngcode.png_file(s, W, H, colour_type) for s in streams]
 
 
+# ---- GIF of device frames (csrc/gif.hip + gifcode.py; video.write_gif, npyframes2video's .gif route) ----------------------
+GIF_SCRATCH_BYTES = 64 << 20           # frames are coded in chunks whose scratch stays below this (one frame is always taken)
+
+
+def _gif_frames(frames, what):
+    """the acceptance rule of ops.png_streams: (uint8 tensor [n,H,W] or [n,H,W,3], colour, mask)"""
+    if not isinstance(frames, torch.Tensor):
+        raise _lib.CsmError("%s: frames must be a device tensor (got %s)" % (what, type(frames).__name__))
+    shape, mask = tuple(frames.shape), frames.dtype == torch.bool
+    if mask:
+        ok, colour = frames.dim() in (2, 3), False
+    else:
+        colour = frames.dim() == 4 or (frames.dim() == 3 and shape[-1] == 3)
+        ok = frames.dtype == torch.uint8 and (frames.dim() in (2, 3) or (frames.dim() == 4 and shape[-1] == 3))
+    if not ok:
+        raise _lib.CsmError("%s: uint8 [n,H,W], [H,W], [n,H,W,3], [H,W,3] or bool [n,H,W], [H,W] expected (got %s %s)"
+                            % (what, frames.dtype, shape))
+    lead = 0 if frames.dim() == (3 if colour else 2) else 1
+    H, W = int(shape[lead]), int(shape[lead + 1])
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError("%s: H and W must be in [1, 65535] (got %dx%d)" % (what, H, W))
+    if not frames.is_cuda:
+        raise _lib.CsmError("%s: frames must be a device tensor; libcsm355 has no CPU path" % what)
+    im = frames.contiguous()
+    im = im.view(torch.uint8) if mask else im
+    return (im if lead else im.unsqueeze(0)), colour, mask
+
+
+def gif_quantize(frames, palette=None, dither='ordered', bgr=True):
+    """Frames to palette indices (contract DESIGN.md §4.10): returns (indices, palette), indices device uint8 [n,H,W], palette host
+    uint8 [256,3] in R, G, B order.  frames: device uint8 [n,H,W,3] or [H,W,3] (B, G, R in memory unless bgr=False), uint8 [n,H,W] or
+    [H,W] (grey) or bool masks (0 / 255); grey and masks keep their bytes as indices into the grey palette, never dithered.  Colour:
+    without `palette` one device pass fills the clip's cell table (csm_gif_histogram), the host reads it once (512 KB) and cuts ONE
+    palette for all frames (gifcode.build_palette); then every pixel takes the nearest of the 256 entries (csm_gif_map), after the
+    8x8 Bayer offset of dither='ordered' or as it is with dither='none'."""
+    from . import gifcode
+    if dither not in ('ordered', 'none'):
+        raise ValueError("gif_quantize: dither must be 'ordered' or 'none' (got %r)" % (dither,))
+    if palette is not None:
+        palette = gifcode.check_palette(palette)
+    im, colour, mask = _gif_frames(frames, "gif_quantize")
+    if not colour:
+        return (im * 255 if mask else im), gifcode.grey_palette()
+    n, H, W = (int(v) for v in im.shape[:3])
+    L, dev, st = _lib.load(), im.device, stream_ptr(im.device)
+    if palette is None:
+        if n * H * W >= gifcode.MAX_PIXELS:
+            raise ValueError("gif_quantize: a clip of %d pixels; the uint32 cell table takes fewer than 2^29" % (n * H * W))
+        table = torch.empty((gifcode.CELLS, 4), dtype=torch.int32, device=dev)
+        check(L.csm_gif_histogram(ptr(im), i64(n * H * W), i32(1 if bgr else 0), ptr(table), st), "gif_histogram")
+        palette = gifcode.build_palette(table.cpu().numpy().view(_np.uint32))     # the one sync of the palette
+    pal_d = torch.from_numpy(palette).to(dev)
+    indices = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+    flags = i32((1 if bgr else 0) | (2 if dither == 'ordered' else 0))
+    check(L.csm_gif_map(ptr(im), i32(n), i32(H), i32(W), flags, ptr(pal_d), ptr(indices), st), "gif_map")
+    return indices, palette
+
+
+def gif_streams(indices):
+    """The LZW data of a GIF's frames (minimum code size 8, not yet framed into sub-blocks; contract DESIGN.md §4.10), one `bytes`
+    per frame of the device uint8 indices [n,H,W] or [H,W]: returns (streams, width, height).  Coding and bit packing run on the
+    device (csm_gif_measure / _write) in chunks of frames whose scratch stays below GIF_SCRATCH_BYTES; per chunk the host reads the
+    byte counts once, then only the compressed bytes."""
+    if not isinstance(indices, torch.Tensor):
+        raise _lib.CsmError("gif_streams: indices must be a device tensor (got %s)" % type(indices).__name__)
+    if indices.dtype != torch.uint8 or indices.dim() not in (2, 3):
+        raise _lib.CsmError("gif_streams: uint8 [n,H,W] or [H,W] indices expected (got %s %s)" % (indices.dtype, tuple(indices.shape)))
+    H, W = (int(v) for v in indices.shape[-2:])
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError("gif_streams: H and W must be in [1, 65535] (got %dx%d)" % (H, W))
+    if not indices.is_cuda:
+        raise _lib.CsmError("gif_streams: indices must be a device tensor; libcsm355 has no CPU path")
+    im = indices.contiguous()                                   # named: alive until the kernels that read it are enqueued
+    im = im.unsqueeze(0) if im.dim() == 2 else im
+    n = int(im.shape[0])
+    L, dev, st = _lib.load(), im.device, stream_ptr(im.device)
+    per_frame = L.csm_gif_scratch_bytes(i32(1), i32(H), i32(W))
+    segments = -(-H * W // 3839)
+    step = max(1, min(GIF_SCRATCH_BYTES // per_frame, (2 ** 24 - 1) // segments))
+    out = []
+    for f0 in range(0, n, step):
+        part = im[f0:f0 + step]
+        k = int(part.shape[0])
+        scratch = torch.empty(L.csm_gif_scratch_bytes(i32(k), i32(H), i32(W)), dtype=torch.uint8, device=dev)
+        counts = torch.empty(k, dtype=torch.int64, device=dev)
+        check(L.csm_gif_measure(ptr(part), i32(k), i32(H), i32(W), ptr(counts), ptr(scratch), st), "gif_measure")
+        counts_h = counts.cpu().numpy()                         # the one sync: the byte counts size the blob exactly
+        padded = (counts_h + 3) & ~3
+        offs = _np.concatenate([[0], _np.cumsum(padded)])
+        total = int(offs[-1])
+        blob = torch.empty(total, dtype=torch.uint8, device=dev)
+        check(L.csm_gif_write(i32(k), i32(H), i32(W), ptr(blob), i64(total), ptr(scratch), st), "gif_write")
+        host = blob.cpu().numpy().tobytes()
+        out += [host[int(o):int(o) + int(b)] for o, b in zip(offs[:-1], counts_h)]
+    return out, W, H
+
+
+def gif_encode(frames, fps=25, loop=0, order=None, dither='ordered', palette=None, bgr=True):
+    """A complete animated GIF (GIF89a; contract DESIGN.md §4.10) of device frames, as `bytes`: gif_quantize, gif_streams, then the
+    host container (gifcode.gif_file: one global 256-colour table, every frame the full canvas for round(100 / fps) centiseconds,
+    `loop` repetitions, 0 = for ever).  `order` lists the coded frame each output frame takes (default: each once, in order)."""
+    from . import gifcode
+    gifcode.delay_cs(fps)                                       # refuse before any device work
+    indices, palette = gif_quantize(frames, palette=palette, dither=dither, bgr=bgr)
+    streams, W, H = gif_streams(indices)
+    return gifcode.gif_file(streams, W, H, palette, fps=fps, loop=loop, order=order)
+
+
 # ---- PatchMatch inpainting (animeinsseg/inpainting/patch_match.py; kenburns_effect.py:497-503) ----------------------------
 def patchmatch_inpaint(img, mask, global_mask=None, patch_size=15, seed=0):
     """PatchMatch inpainting of device uint8 [H,W,3] `img` where the device uint8 `mask` ([H,W] or [H,W,1]) is non-zero;

@@ -1,5 +1,5 @@
-"""Motion-JPEG AVI container and animated-PNG container (pure host code): the video files of the Ken Burns path, from frames
-that ops.jpeg_encode / ops.png_streams compressed on the device.
+"""Motion-JPEG AVI container, animated-PNG container and animated-GIF file (pure host code): the video files of the Ken Burns path,
+from frames that ops.jpeg_encode / ops.png_streams / ops.gif_streams compressed on the device.
 
 A classic RIFF AVI (AVI 1.0, no OpenDML extension, so below 2 GiB):
 
@@ -19,6 +19,8 @@ An APNG (APNG specification 1.0) is a PNG whose first frame is the default image
     fcTL (sequence 0), IDAT <zlib stream of frame 0>
     fcTL, fdAT <sequence number + zlib stream> ...      per further output frame; sequence numbers count fcTL and fdAT together
     IEND
+
+An animated GIF (GIF89a) is laid out by gifcode.gif_file.
 """
 import struct
 
@@ -106,6 +108,18 @@ def write_apng(path, streams, width, height, colour_type, fps=25, order=None):
             seq += 1
     parts.append(chunk(b'IEND', b''))
     data = b''.join(parts)
+    with open(path, 'wb') as f:
+        f.write(data)
+    return len(data)
+
+
+def write_gif(path, streams, width, height, palette, fps=25, loop=0, order=None):
+    """Write the LZW streams `streams` (a list of bytes from ops.gif_streams, all width x height, indices into the uint8 [256,3]
+    R, G, B `palette`) as an animated GIF that shows every frame for round(100 / fps) centiseconds and repeats `loop` times (0: for
+    ever).  `order` as in write_mjpeg_avi: a frame is coded once and may be written several times.  Returns the number of bytes
+    written."""
+    from .gifcode import gif_file
+    data = gif_file(streams, width, height, palette, fps=fps, loop=loop, order=order)
     with open(path, 'wb') as f:
         f.write(data)
     return len(data)

@@ -603,6 +603,29 @@ int csm_png_decode_desc_words(void);
 int csm_png_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
                    void *scratch, int *info_host, void *stream);
 
+/* The device half of a GIF file (gif.hip; contract DESIGN.md §4.10, restated in tests/gif_restatement.py, byte-identical): one
+ * 256-colour palette per clip and the LZW stream (minimum code size 8) of every frame.  1 <= H, W <= 65535.
+ * csm_gif_histogram: frames u8 [pixels][3], contiguous; flags bit 0 = the channels are B, G, R in memory.  table device uint32
+ *   [32768][4], zeroed by the call: per cell (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) the pixel count and the sums of r & 7,
+ *   g & 7, b & 7.  pixels < 2^29, so no sum wraps.  The host cuts the palette from it (gifcode.build_palette).
+ * csm_gif_map: frames u8 [n,H,W,3]; flags bit 0 as above, bit 1 = ordered dither (an 8x8 Bayer offset in [-4, 3] by (y & 7, x & 7),
+ *   clamped); palette device u8 [256][3] R, G, B; indices u8 [n,H,W] = the entry nearest in squared distance over all 256 (the
+ *   lowest index on ties); a pixel that equals an entry takes it whatever the dither.
+ * csm_gif_measure: indices u8 [n,H,W], contiguous, n * ceil(H * W / 3839) < 2^24.  Every segment of 3839 pixels is coded by greedy
+ *   LZW from a Clear code; bytes device int64 [n] receives the bytes of each frame's stream (at most
+ *   (12 * (H * W + segments + 1) + 7) / 8).  scratch: csm_gif_scratch_bytes(n, H, W) device bytes (0 for an invalid shape), shared
+ *   with the write call: 2 B per pixel for the codes and 12 B per segment, 16 B per frame.
+ * csm_gif_write: out: out_bytes device bytes (a multiple of 4, 4-aligned), zeroed by the call; frame f's stream starts at the sum of
+ *   the streams before it, each rounded up to 4 bytes: Clear, codes, ..., EOI, LSB-first, zero bits to the next byte.  Nothing is
+ *   written at or past a stream's bytes rounded up to 4, nor past out_bytes.  Same n, H, W and scratch as the measure call.
+ * Async on the stream, no allocation, no sync; the only atomics are integer adds (the table) and integer ORs of disjoint bits, so
+ * the output is deterministic. */
+size_t csm_gif_scratch_bytes(int n, int H, int W);
+int csm_gif_histogram(const uint8_t *frames, int64_t pixels, int flags, uint32_t *table, void *stream);
+int csm_gif_map(const uint8_t *frames, int n, int H, int W, int flags, const uint8_t *palette, uint8_t *indices, void *stream);
+int csm_gif_measure(const uint8_t *indices, int n, int H, int W, int64_t *bytes, void *scratch, void *stream);
+int csm_gif_write(int n, int H, int W, uint8_t *out, int64_t out_bytes, void *scratch, void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */
