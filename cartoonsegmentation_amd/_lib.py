@@ -58,6 +58,7 @@ def load():
         _lib.csm_png_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_jpeg_decode_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_png_decode_scratch_bytes.restype = ctypes.c_size_t
+        _lib.csm_jpeg_decode_progressive_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_frame_glue_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_leres_post_scratch_bytes.restype = ctypes.c_size_t
         if os.environ.get("CSM_TUNER_OPTIONS"):          # measurement aid (A/B of launch forms, include/csm355.h csm_debug_conv_tuner_options); speed only

@@ -4,6 +4,11 @@ csrc/jpegdec.hip reads.
     probe(data)        a plain description of a baseline JPEG file (size, components, tables, restart interval, the byte range of
                        the entropy-coded segment, EXIF orientation), or Unsupported(reason) for a stream the decoder does not take.
                        Reads marker segments only, never entropy data, and checks every segment length against the buffer.
+                       With progressive=True a progressive file (SOF2) is described too: 'scans' lists its scans.
+    scan_levels(info)  the scans of a progressive file by dependency level
+    scan_tables(info)  the decode tables of each scan of a progressive file
+    scan_intervals(..) where the restart intervals of a scan begin
+    scan_descriptor(..) the int32 row of csm_jpeg_decode_progressive for one scan
     huffman_table(..)  the decode table of one Huffman code as the kernels read it (TABLE_BYTES bytes)
     file_tables(info)  the table region of one file: HUFF_SLOTS decode tables and the quantisation tables in natural order
     descriptor(..)     the int32 row of csm_jpeg_decode for one file
@@ -84,12 +89,175 @@ def _entropy_end(data, start):
             return p, m
 
 
-def probe(data):
+def _take_dht(seg, huffman):
+    q = 0
+    while q < len(seg):
+        if q + 17 > len(seg):
+            raise Unsupported("malformed DHT segment")
+        tc, th = seg[q] >> 4, seg[q] & 15
+        bits = list(seg[q + 1:q + 17])
+        cnt = sum(bits)
+        if tc > 1 or th > 3 or q + 17 + cnt > len(seg):
+            raise Unsupported("malformed DHT segment")
+        vals = list(seg[q + 17:q + 17 + cnt])
+        if not _check_huffman(bits, vals):
+            raise Unsupported("malformed DHT segment: not a prefix code")
+        huffman[(tc, th)] = (bits, vals)
+        q += 17 + cnt
+
+
+def _take_dqt(seg, qtables):
+    q = 0
+    while q < len(seg):
+        pq, tq = seg[q] >> 4, seg[q] & 15
+        if pq != 0:
+            raise Unsupported("16-bit quantisation tables")
+        if tq > 3 or q + 65 > len(seg):
+            raise Unsupported("malformed DQT segment")
+        qtables[tq] = list(seg[q + 1:q + 65])
+        q += 65
+
+
+def _take_dri(seg):
+    if len(seg) != 2:
+        raise Unsupported("malformed DRI segment")
+    return (seg[0] << 8) | seg[1]
+
+
+MAX_SCANS = 64
+MAX_AL = 13
+
+
+def _progressive_scans(data, p, frame, qtables, huffman, ri):
+    """The scans of a progressive file from the first SOS (its length field at `p`) to EOI: the list of probe's 'scans', and the
+    restart interval in force at the end.  Checks the scan script (T.81 G.1.1.1.1 and the rules of DESIGN.md §4.11)."""
+    n = len(data)
+    comps = frame['components']
+    nc = len(comps)
+    ids = [c['id'] for c in comps]
+    cur = [[None] * 64 for _ in range(nc)]              # the point transform each coefficient stands at; None: no scan yet
+    scans = []
+    total = 0
+    while True:
+        ln = (data[p] << 8) | data[p + 1]
+        seg = data[p + 2:p + ln]
+        if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
+            raise Unsupported("malformed SOS segment")
+        ns = seg[0]
+        if not 1 <= ns <= nc:
+            raise Unsupported("malformed SOS segment: %d components in a scan of a %d-component frame" % (ns, nc))
+        sc = []
+        for i in range(ns):
+            cid, t = seg[1 + 2 * i], seg[2 + 2 * i]
+            if cid not in ids:
+                raise Unsupported("malformed SOS segment: unknown component %d" % cid)
+            ci = ids.index(cid)
+            if sc and ci <= sc[-1][0]:
+                raise Unsupported("the scan's components are not in frame order")
+            if (t >> 4) > 3 or (t & 15) > 3:
+                raise Unsupported("malformed SOS segment: Huffman table id above 3")
+            sc.append((ci, t >> 4, t & 15))
+        ss, se, ah, al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+        if ss > 63 or se > 63 or se < ss:
+            raise Unsupported("malformed SOS segment: spectral selection %d..%d" % (ss, se))
+        if ss == 0:
+            if se != 0:
+                raise Unsupported("a scan that mixes DC and AC coefficients (spectral selection 0..%d)" % se)
+            if ns != nc and ns != 1:
+                raise Unsupported("a DC scan of %d of %d components" % (ns, nc))
+        else:
+            if ns != 1:
+                raise Unsupported("an interleaved AC scan (%d components)" % ns)
+            if cur[sc[0][0]][0] is None:
+                raise Unsupported("an AC scan of component %d before its DC scan" % sc[0][0])
+        if al > MAX_AL:
+            raise Unsupported("successive approximation: point transform %d above %d" % (al, MAX_AL))
+        if ah != 0 and ah != al + 1:
+            raise Unsupported("successive approximation: a refinement from bit %d to bit %d (one bit per scan is taken)" % (ah, al))
+        for ci, _, _ in sc:
+            for k in range(ss, se + 1):
+                have = cur[ci][k]
+                if ah == 0:
+                    if have is not None:
+                        raise Unsupported("coefficient %d of component %d has two first scans" % (k, ci))
+                elif have != ah:
+                    raise Unsupported("a refinement of coefficient %d of component %d from bit %d, which stands at %s"
+                                      % (k, ci, ah, "no scan" if have is None else "bit %d" % have))
+                cur[ci][k] = al
+        need = [] if ah else ([(0, td) for _, td, _ in sc] if ss == 0 else [(1, sc[0][2])])
+        for key in need:
+            if key not in huffman:
+                raise Unsupported("missing %s Huffman table %d" % ("AC" if key[0] else "DC", key[1]))
+        start = p + ln
+        end, m = _entropy_end(data, start)
+        if end is None:
+            raise Unsupported("truncated file: no EOI marker")
+        total += end - start
+        if total > MAX_ENTROPY_BYTES:
+            raise Unsupported("more than %d bytes of entropy data" % MAX_ENTROPY_BYTES)
+        scans.append({'components': sc, 'ss': ss, 'se': se, 'ah': ah, 'al': al, 'entropy': (start, end), 'restart_interval': ri,
+                      'huffman': dict(huffman)})
+        if len(scans) > MAX_SCANS:
+            raise Unsupported("more than %d scans" % MAX_SCANS)
+        if m == 0xD9:
+            break
+        # the segments between two scans
+        p = end
+        while True:
+            while p < n and data[p] == 0xFF:
+                p += 1
+            if p >= n:
+                raise Unsupported("truncated file: no EOI marker")
+            m = data[p]
+            p += 1
+            if m == 0xD9:
+                break
+            if m == 0xDC:
+                raise Unsupported("DNL")
+            if m not in (0xC4, 0xDA, 0xDB, 0xDD, 0xFE) and not 0xE0 <= m <= 0xEF:
+                raise Unsupported("marker FF%02X between two scans" % m)
+            if p + 2 > n:
+                raise Unsupported("truncated file: cut inside a segment")
+            ln = (data[p] << 8) | data[p + 1]
+            if ln < 2 or p + ln > n:
+                raise Unsupported("truncated file: cut inside a segment (marker FF%02X at offset %d)" % (m, p - 2))
+            if m == 0xDA:
+                break
+            seg = data[p + 2:p + ln]
+            if m == 0xC4:
+                _take_dht(seg, huffman)
+            elif m == 0xDB:
+                _take_dqt(seg, qtables)
+            elif m == 0xDD:
+                ri = _take_dri(seg)
+            p += ln
+            if p >= n or data[p] != 0xFF:
+                raise Unsupported("malformed file: no marker at offset %d" % p)
+        if m == 0xD9:
+            break
+    for ci in range(nc):
+        left = [k for k in range(64) if cur[ci][k] != 0]
+        if left:
+            raise Unsupported("the file ends before full precision: coefficient %d of component %d %s"
+                              % (left[0], ci, "has no scan" if cur[ci][left[0]] is None else "stands at bit %d" % cur[ci][left[0]]))
+    return scans, ri
+
+
+def probe(data, progressive=False):
     """Description of the baseline JPEG file `data` (bytes): a dict with 'height', 'width', 'sof' (0 or 1), 'components' (a list of
     {'id', 'h', 'v', 'tq', 'td', 'ta'} in scan order), 'qtables' ({id: 64 entries in zigzag order}), 'huffman' ({(class, id): (BITS
     [16], HUFFVAL)}, class 0 = DC, 1 = AC), 'restart_interval' (0 = none), 'entropy' ((start, end): the bytes between SOS and
     EOI), 'orientation' (EXIF, 1..8 or None), 'jfif' and 'adobe_transform' (None without an Adobe segment).  Raises Unsupported
-    with a reason for everything else, a truncated or malformed file included."""
+    with a reason for everything else, a truncated or malformed file included.
+
+    'progressive' is False for these.  With progressive=True a progressive file (SOF2, Huffman) is described as well: 'sof' is 2,
+    'progressive' True, 'components' carry no 'td' / 'ta', 'entropy' spans all scans, and 'scans' lists in file order
+        {'components': [(component index, td, ta)], 'ss', 'se', 'ah', 'al', 'entropy': (start, end), 'restart_interval',
+         'huffman': {(class, id): (BITS, HUFFVAL)}}
+    with the Huffman tables and the restart interval in force at that SOS.  The scan script must satisfy T.81 G.1.1.1.1 and: a DC
+    scan holds all components or one; an AC scan follows its component's first DC scan; every refinement lowers the point
+    transform by one bit; no coefficient has two first scans; at EOI every coefficient of every component stands at bit 0; at
+    most MAX_SCANS scans.  Each other script raises Unsupported with its own reason."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise TypeError("probe: bytes expected (got %s)" % type(data).__name__)
     data = bytes(data)
@@ -128,7 +296,9 @@ def probe(data):
         if ln < 2 or p + ln > n:
             raise Unsupported("truncated file: cut inside a segment (marker FF%02X at offset %d)" % (m, p - 2))
         seg = data[p + 2:p + ln]
-        if m in (0xC0, 0xC1):
+        if m == 0xC2 and not progressive:
+            raise Unsupported("progressive (SOF2)")
+        if m in (0xC0, 0xC1, 0xC2):
             if frame is not None:
                 raise Unsupported("several frames")
             if len(seg) < 6:
@@ -144,8 +314,6 @@ def probe(data):
                 raise Unsupported("malformed SOF segment: width 0")
             comps = [{'id': seg[6 + 3 * i], 'h': seg[7 + 3 * i] >> 4, 'v': seg[7 + 3 * i] & 15, 'tq': seg[8 + 3 * i]} for i in range(nf)]
             frame = {'sof': m - 0xC0, 'height': H, 'width': W, 'components': comps}
-        elif m == 0xC2:
-            raise Unsupported("progressive (SOF2)")
         elif m in (0xC3, 0xC5, 0xC6, 0xC7):
             raise Unsupported("lossless or hierarchical coding (SOF%d)" % (m - 0xC0))
         elif m in (0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF):
@@ -153,34 +321,11 @@ def probe(data):
         elif m == 0xC8:
             raise Unsupported("reserved JPEG extension marker")
         elif m == 0xC4:
-            q = 0
-            while q < len(seg):
-                if q + 17 > len(seg):
-                    raise Unsupported("malformed DHT segment")
-                tc, th = seg[q] >> 4, seg[q] & 15
-                bits = list(seg[q + 1:q + 17])
-                cnt = sum(bits)
-                if tc > 1 or th > 3 or q + 17 + cnt > len(seg):
-                    raise Unsupported("malformed DHT segment")
-                vals = list(seg[q + 17:q + 17 + cnt])
-                if not _check_huffman(bits, vals):
-                    raise Unsupported("malformed DHT segment: not a prefix code")
-                huffman[(tc, th)] = (bits, vals)
-                q += 17 + cnt
+            _take_dht(seg, huffman)
         elif m == 0xDB:
-            q = 0
-            while q < len(seg):
-                pq, tq = seg[q] >> 4, seg[q] & 15
-                if pq != 0:
-                    raise Unsupported("16-bit quantisation tables")
-                if tq > 3 or q + 65 > len(seg):
-                    raise Unsupported("malformed DQT segment")
-                qtables[tq] = list(seg[q + 1:q + 65])
-                q += 65
+            _take_dqt(seg, qtables)
         elif m == 0xDD:
-            if len(seg) != 2:
-                raise Unsupported("malformed DRI segment")
-            ri = (seg[0] << 8) | seg[1]
+            ri = _take_dri(seg)
         elif m == 0xDC:
             raise Unsupported("DNL")
         elif m == 0xE0:
@@ -196,6 +341,8 @@ def probe(data):
         elif m == 0xDA:
             if frame is None:
                 raise Unsupported("malformed file: SOS before SOF")
+            if frame['sof'] == 2:
+                break                              # the scans of a progressive file are read below, from this SOS
             if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
                 raise Unsupported("malformed SOS segment")
             ns = seg[0]
@@ -232,6 +379,15 @@ def probe(data):
         if not (1 <= comps[0]['h'] <= 4 and 1 <= comps[0]['v'] <= 4):
             raise Unsupported("malformed SOF segment: sampling factor 0")
         comps[0]['h'] = comps[0]['v'] = 1        # a one-component scan is not interleaved: its sampling factors do not matter
+    if frame['sof'] == 2:
+        scans, ri = _progressive_scans(data, p, frame, qtables, huffman, ri)
+        for c in comps:
+            if c['tq'] not in qtables:
+                raise Unsupported("missing quantisation table %d" % c['tq'])
+        out = dict(frame)
+        out.update(qtables=qtables, huffman=huffman, restart_interval=ri, entropy=(scans[0]['entropy'][0], scans[-1]['entropy'][1]),
+                   orientation=orientation, jfif=jfif, adobe_transform=adobe, progressive=True, scans=scans)
+        return out
     for c in comps:
         if c['tq'] not in qtables:
             raise Unsupported("missing quantisation table %d" % c['tq'])
@@ -250,7 +406,7 @@ def probe(data):
         raise Unsupported("more than %d bytes of entropy data" % MAX_ENTROPY_BYTES)
     out = dict(frame)
     out.update(qtables=qtables, huffman=huffman, restart_interval=ri, entropy=(start, end), orientation=orientation, jfif=jfif,
-               adobe_transform=adobe)
+               adobe_transform=adobe, progressive=False)
     return out
 
 
@@ -318,4 +474,77 @@ def descriptor(info, ent_off, tab_off, out_off):
     d[9:9 + len(comps)] = dcs
     d[12:12 + len(comps)] = acs
     d[15], d[16] = out_off & 0x7FFFFFFF, out_off >> 31
+    return d
+
+
+# ---- progressive files (csrc/jpegprog.hip) ------------------------------------------------------------------
+SCAN_DESC_WORDS = 16
+
+
+def scan_levels(info):
+    """The scans of a progressive file by dependency level: scan j depends on scan i < j when they share a component and their
+    coefficient ranges intersect; a scan's level is one more than the highest level it depends on.  A list of lists of scan indices;
+    the scans of one level write disjoint coefficients."""
+    scans = info['scans']
+    level = []
+    for j, b in enumerate(scans):
+        lv = 0
+        cb = {c for c, _, _ in b['components']}
+        for i in range(j):
+            a = scans[i]
+            if cb & {c for c, _, _ in a['components']} and a['ss'] <= b['se'] and b['ss'] <= a['se']:
+                lv = max(lv, level[i] + 1)
+        level.append(lv)
+    return [[j for j in range(len(scans)) if level[j] == lv] for lv in range(max(level) + 1)]
+
+
+def scan_tables(info):
+    """Per scan of a progressive file its decode tables as the kernels read them (huffman_table, TABLE_BYTES bytes each): one DC
+    table per component of a DC first scan (in the scan's component order), one AC table for an AC scan, none for a DC
+    refinement.  A list of uint8 arrays."""
+    out = []
+    for sc in info['scans']:
+        if sc['ss'] == 0:
+            keys = [] if sc['ah'] else [(0, td) for _, td, _ in sc['components']]
+        else:
+            keys = [(1, sc['components'][0][2])]
+        parts = []
+        for key in keys:
+            lut, maxcode, valoff, v = huffman_table(*sc['huffman'][key])
+            parts += [lut.view(np.uint8), maxcode.view(np.uint8), valoff.view(np.uint8), v]
+        out.append(np.concatenate(parts) if parts else np.zeros(0, np.uint8))
+    return out
+
+
+def scan_block_count(info, sc):
+    """(blocks, blocks per restart unit) of a scan: a scan of all components walks the padded MCU grid, a one-component scan only
+    the component's true block grid, ceil(ceil(W h / hmax) / 8) by ceil(ceil(H v / vmax) / 8), and its restart interval counts
+    blocks"""
+    comps = info['components']
+    hs, vs = comps[0]['h'], comps[0]['v']
+    H, W = info['height'], info['width']
+    if len(sc['components']) > 1:
+        bpm = hs * vs + len(comps) - 1
+        return -(-W // (8 * hs)) * -(-H // (8 * vs)) * bpm, bpm
+    c = comps[sc['components'][0][0]]
+    return -(-(-(-W * c['h'] // hs)) // 8) * -(-(-(-H * c['v'] // vs)) // 8), 1
+
+
+def scan_intervals(data, sc):
+    """int32 [restart intervals]: the byte of the scan's entropy data at which each restart interval begins ([0] = 0, then the
+    byte behind every RSTn marker).  Inside entropy-coded data an FF followed by D0..D7 is always a marker."""
+    s, e = sc['entropy']
+    raw = np.frombuffer(data, np.uint8, e - s, s)
+    at = np.nonzero((raw[:-1] == 0xFF) & (raw[1:] >= 0xD0) & (raw[1:] <= 0xD7))[0] if e - s > 1 else np.zeros(0, np.int64)
+    return np.concatenate([[0], at + 2]).astype(np.int32)
+
+
+def scan_descriptor(info, j, file_index, ent_off, tab_off, level, iv_off=0):
+    """the int32 [SCAN_DESC_WORDS] row of csm_jpeg_decode_progressive (include/csm355.h) for scan j of a progressive file that is file
+    `file_index` of the call, whose entropy bytes lie at `ent_off` and whose tables (scan_tables) at `tab_off` of the blob; `iv_off`
+    is where the blob holds scan_intervals (refinement scans with restart markers)"""
+    sc = info['scans'][j]
+    d = np.zeros(SCAN_DESC_WORDS, np.int32)
+    d[0:7] = (file_index, len(sc['components']), sc['components'][0][0], sc['ss'], sc['se'], sc['ah'], sc['al'])
+    d[7:13] = (ent_off, sc['entropy'][1] - sc['entropy'][0], sc['restart_interval'], tab_off, level, iv_off)
     return d

@@ -675,7 +675,7 @@ def jpeg_encode(frames, quality=90, subsampling='420'):
 JPEG_DECODE_SCRATCH_BYTES = 64 << 20   # files are decoded in chunks whose scratch stays below this (one file is always taken)
 
 
-def jpeg_decode(files, device=None, stats=None, _infos=None):
+def jpeg_decode(files, device=None, stats=None, _infos=None, progressive=False):
     """Baseline JPEG files (contract DESIGN.md §4.8) to device uint8 [H,W,3] tensors in B, G, R order.  `files` is one `bytes` (one
     tensor is returned) or a list of `bytes` (a list is returned); sizes and modes (grey, 4:4:4, 4:2:2, 4:2:0, with or without
     restart markers) may differ within a call.  A grey file gives three equal channels.  EXIF orientation is NOT applied.  The
@@ -683,21 +683,69 @@ def jpeg_decode(files, device=None, stats=None, _infos=None):
     files' entropy bytes and tables; Huffman decoding, the inverse DCT, chroma upsampling and colour conversion run on the device
     (csm_jpeg_decode) in chunks of files whose scratch stays below JPEG_DECODE_SCRATCH_BYTES.  Corrupt entropy data raises
     CsmError.  The tensors of a chunk are views of one allocation.  `stats` (a dict) receives 'passes': the synchronisation passes
-    between workgroups of every chunk."""
-    import ctypes
+    between workgroups of every chunk.
+
+    progressive=True also takes progressive files (SOF2; jpegcode.probe(data, progressive=True) names the scan
+    scripts that are taken), mixed with baseline files in any order: the baseline files of the call go through csm_jpeg_decode, the
+    progressive ones through csm_jpeg_decode_progressive, each in chunks under the same budget, and the tensors come back in the
+    order of `files`.  `stats` then also receives 'progressive' (the indices of the progressive files), 'levels' (the dependency
+    levels launched for every progressive chunk) and 'progressive_passes'."""
     from . import jpegcode
     single = isinstance(files, (bytes, bytearray, memoryview))
     datas = [files] if single else list(files)
     for d in datas:
         if not isinstance(d, (bytes, bytearray, memoryview)):
             raise TypeError("jpeg_decode: bytes or a list of bytes expected (got %s)" % type(d).__name__)
-    infos = _infos if _infos is not None else [jpegcode.probe(d) for d in datas]
+    if _infos is not None:
+        infos = _infos
+    elif progressive:
+        infos = [jpegcode.probe(d, progressive=True) for d in datas]
+    else:
+        infos = [jpegcode.probe(d) for d in datas]
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     if dev.type != 'cuda':
         raise _lib.CsmError("jpeg_decode: the device must be a GPU (got %s); libcsm355 has no CPU path" % dev)
     if dev.index is None:
         dev = torch.device('cuda', torch.cuda.current_device())
     L = _lib.load()
+    prog = [i for i, info in enumerate(infos) if info.get('progressive')]
+    if prog and not progressive:
+        raise jpegcode.Unsupported("progressive (SOF2)")
+    base = [i for i in range(len(datas)) if not infos[i].get('progressive')]
+    out = [None] * len(datas)
+    passes = []
+    if base:
+        tensors, passes = _jpeg_decode_baseline(L, [datas[i] for i in base], [infos[i] for i in base], dev)
+        for i, t in zip(base, tensors):
+            out[i] = t
+    if stats is not None:
+        stats['passes'] = passes
+    if progressive:
+        levels, ppasses = [], []
+        if prog:
+            tensors, levels, ppasses = _jpeg_decode_progressive(L, [datas[i] for i in prog], [infos[i] for i in prog], dev)
+            for i, t in zip(prog, tensors):
+                out[i] = t
+        if stats is not None:
+            stats.update(progressive=prog, levels=levels, progressive_passes=ppasses)
+    return out[0] if single else out
+
+
+def _jpeg_chunks(own):
+    """runs of consecutive files whose scratch (own[i] bytes each) stays below JPEG_DECODE_SCRATCH_BYTES; one file is always taken"""
+    i = 0
+    while i < len(own):
+        k, total = 1, own[i]
+        while i + k < len(own) and total + own[i + k] <= JPEG_DECODE_SCRATCH_BYTES:
+            total += own[i + k]
+            k += 1
+        yield i, k
+        i += k
+
+
+def _jpeg_decode_baseline(L, datas, infos, dev):
+    import ctypes
+    from . import jpegcode
     words = L.csm_jpeg_decode_desc_words()
     assert words == jpegcode.DESC_WORDS
     c_desc = ctypes.POINTER(ctypes.c_int32)
@@ -707,14 +755,8 @@ def jpeg_decode(files, device=None, stats=None, _infos=None):
 
     own = [scratch_bytes(jpegcode.descriptor(info, 0, 0, 0).reshape(1, -1)) for info in infos]
     out, passes = [], []
-    i = 0
-    while i < len(datas):
-        k, total = 1, own[i]
-        while i + k < len(datas) and total + own[i + k] <= JPEG_DECODE_SCRATCH_BYTES:
-            total += own[i + k]
-            k += 1
+    for i, k in _jpeg_chunks(own):
         part = list(zip(datas[i:i + k], infos[i:i + k]))
-        i += k
         # the blob: every file's table region, then every file's entropy bytes, each on a 16-byte boundary
         ent_off, o = [], k * jpegcode.FILE_TABLE_BYTES
         for _, info in part:
@@ -744,9 +786,97 @@ def jpeg_decode(files, device=None, stats=None, _infos=None):
         for j, (_, info) in enumerate(part):
             H, W = info['height'], info['width']
             out.append(pixels[out_off[j]:out_off[j] + H * W * 3].view(H, W, 3))
-    if stats is not None:
-        stats['passes'] = passes
-    return out[0] if single else out
+    return out, passes
+
+
+def _jpeg_decode_progressive(L, datas, infos, dev):
+    """the progressive files of jpeg_decode: (tensors, levels per chunk, synchronisation passes per chunk)"""
+    import ctypes
+    from . import jpegcode
+    words, swords = L.csm_jpeg_decode_desc_words(), L.csm_jpeg_decode_scan_desc_words()
+    assert words == jpegcode.DESC_WORDS and swords == jpegcode.SCAN_DESC_WORDS
+    c_desc = ctypes.POINTER(ctypes.c_int32)
+    a16 = lambda v: (v + 15) & ~15
+
+    def layout(part):
+        """the blob of a chunk: every file's table region (its quantisation tables), then per scan its decode tables, its entropy
+        bytes and, for a refinement with restart markers, where its intervals begin, each on a 16-byte boundary"""
+        k = len(part)
+        o = k * jpegcode.FILE_TABLE_BYTES
+        pieces, rows = [], []
+        desc = _np.zeros((k, words), _np.int32)
+        out_off, oo = [], 0
+        for j, (d, info) in enumerate(part):
+            head = dict(info, restart_interval=0, components=[dict(c, td=0, ta=0) for c in info['components']], huffman={}, entropy=(0, 0))
+            desc[j] = jpegcode.descriptor(head, 0, j * jpegcode.FILE_TABLE_BYTES, oo)
+            out_off.append(oo)
+            oo += a16(info['height'] * info['width'] * 3)
+            level_of = {s: lv for lv, ss in enumerate(jpegcode.scan_levels(info)) for s in ss}
+            tabs = jpegcode.scan_tables(info)
+            for si, sc in enumerate(info['scans']):
+                tab_off = o
+                if tabs[si].size:
+                    pieces.append((o, tabs[si]))
+                    o += a16(tabs[si].size)
+                s, e = sc['entropy']
+                ent_off = o
+                pieces.append((o, _np.frombuffer(d, _np.uint8, e - s, s)))
+                o += a16(e - s)
+                iv_off = 0
+                blocks, unit = jpegcode.scan_block_count(info, sc)
+                per = sc['restart_interval'] * unit
+                if sc['ah'] and per and blocks > per:
+                    want = -(-blocks // per)
+                    iv = jpegcode.scan_intervals(d, sc)[:want]
+                    iv = _np.concatenate([iv, _np.full(want - iv.size, e - s, _np.int32)])      # a missing marker: no data
+                    iv_off = o
+                    pieces.append((o, iv.view(_np.uint8)))
+                    o += a16(iv.size * 4)
+                rows.append(jpegcode.scan_descriptor(info, si, j, ent_off, tab_off, level_of[si], iv_off))
+        return o, pieces, desc, _np.stack(rows), out_off, oo
+
+    def quant_only(info):
+        t = _np.zeros(jpegcode.FILE_TABLE_BYTES, _np.uint8)
+        q = _np.zeros((3, 64), _np.uint16)
+        for i, c in enumerate(info['components']):
+            q[i, list(jpegcode.ZIGZAG)] = info['qtables'][c['tq']]
+        t[jpegcode.HUFF_SLOTS * jpegcode.TABLE_BYTES:] = q.view(_np.uint8).ravel()
+        return t
+
+    def scratch_bytes(desc, sdesc):
+        return L.csm_jpeg_decode_progressive_scratch_bytes(desc.ctypes.data_as(c_desc), i32(desc.shape[0]),
+                                                           sdesc.ctypes.data_as(c_desc), i32(sdesc.shape[0]))
+
+    own = []
+    for d, info in zip(datas, infos):
+        _, _, desc, sdesc, _, _ = layout([(d, info)])
+        own.append(scratch_bytes(desc, sdesc))
+    out, levels, passes = [], [], []
+    for i, k in _jpeg_chunks(own):
+        part = list(zip(datas[i:i + k], infos[i:i + k]))
+        o, pieces, desc, sdesc, out_off, oo = layout(part)
+        blob_h = _np.zeros(max(o, 16), _np.uint8)
+        for j, (_, info) in enumerate(part):
+            blob_h[j * jpegcode.FILE_TABLE_BYTES:(j + 1) * jpegcode.FILE_TABLE_BYTES] = quant_only(info)
+        for at, arr in pieces:
+            blob_h[at:at + arr.size] = arr
+        with torch.cuda.device(dev):
+            blob = torch.from_numpy(blob_h).to(dev)
+            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
+            need = scratch_bytes(desc, sdesc)
+            if need == 0:
+                raise _lib.CsmError("jpeg_decode: %s" % L.csm_last_error().decode())
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+            info_h = (ctypes.c_int * 4)()
+            check(L.csm_jpeg_decode_progressive(ptr(blob), i64(blob.numel()), desc.ctypes.data_as(c_desc), i32(k),
+                                                sdesc.ctypes.data_as(c_desc), i32(sdesc.shape[0]), ptr(pixels), i64(oo),
+                                                ptr(scratch), info_h, stream_ptr(dev)), "jpeg_decode_progressive")
+        passes.append(int(info_h[0]))
+        levels.append(int(info_h[1]))
+        for j, (_, info) in enumerate(part):
+            H, W = info['height'], info['width']
+            out.append(pixels[out_off[j]:out_off[j] + H * W * 3].view(H, W, 3))
+    return out, levels, passes
 
 
 # ---- PNG files to device frames (csrc/pngdec.hip + pngread.py; utils.io_utils.imread_device) ------------------------------------

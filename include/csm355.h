@@ -581,6 +581,32 @@ int csm_jpeg_decode_desc_words(void);
 int csm_jpeg_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
                     void *scratch, int *info_host, void *stream);
 
+/* Progressive JPEG files (SOF2, Huffman) to uint8 B, G, R pixels (jpegprog.hip; contract DESIGN.md §4.11, the coefficient decode
+ * restated in tests/jpegprog_restatement.py, byte-identical; the pixels are csm_jpeg_decode's).  The host parses the markers and
+ * checks the scan script (jpegcode.probe(data, progressive=True)); files of different sizes, modes and scripts share a call.
+ * desc_host: one csm_jpeg_decode row per file, validated as there; [5] .. [7] (restart interval, entropy range: 0, 0, 0 will do)
+ *   and [9] .. [14] (table slots) are not used; [8] is the file's table region, of which only the quantisation tables are read.
+ * scan_desc_host: host int32 [n_scans][csm_jpeg_decode_scan_desc_words() = 16], any order: [0] file (index into desc_host),
+ *   [1] components of the scan (1, or all of the file's for a DC scan), [2] the first component's index, [3] [4] Ss Se, [5] [6] Ah Al
+ *   (Ah = 0 or Al + 1, Al <= 13), [7] [8] offset and length of the scan's entropy-coded bytes in the blob, [9] the restart interval
+ *   in force (MCUs in a scan of all components, else blocks), [10] offset (a multiple of 4) of the scan's decode tables in the blob
+ *   (912 bytes each as in csm_jpeg_decode: one DC table per component of a DC first scan, one AC table for an AC scan, none for a
+ *   DC refinement), [11] dependency level (0..63; the scans of one level must write disjoint coefficients, and a scan's level is
+ *   above that of every earlier scan of the file whose coefficients it meets: jpegcode.scan_levels), [12] refinement scans with more than
+ *   one restart interval: offset (a multiple of 4) in the blob of int32 [intervals], the byte of the scan's entropy data at which each
+ *   interval begins ([0] = 0); the rest 0.  1 <= n_scans <= 64 n.
+ * scratch: csm_jpeg_decode_progressive_scratch_bytes(...) device bytes (0 for invalid descriptors): csm_jpeg_decode's, 28 B per
+ *   subsequence of every first scan, 8 B per block of every AC refinement scan.
+ * csm_jpeg_decode_progressive: info_host (may be NULL) receives [0] the synchronisation passes between workgroups, [1] the levels
+ *   launched, [2] [3] 0.  The call SYNCHRONISES the stream: once per pass and once at the end.  Returns CSM_ERR_DATA for corrupt
+ *   entropy data (an invalid code, a refinement symbol of size above 1, a coefficient placed past its band, a scan whose data do not
+ *   hold its blocks exactly); whatever the data and whatever [12] points at, no read leaves a scan's entropy bytes and no store the
+ *   file's blocks.  No kernel waits on another workgroup; the output is deterministic. */
+size_t csm_jpeg_decode_progressive_scratch_bytes(const int32_t *desc_host, int n, const int32_t *scan_desc_host, int n_scans);
+int csm_jpeg_decode_scan_desc_words(void);
+int csm_jpeg_decode_progressive(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, const int32_t *scan_desc_host,
+                                int n_scans, uint8_t *out, int64_t out_bytes, void *scratch, int *info_host, void *stream);
+
 /* PNG files to uint8 B, G, R pixels (pngdec.hip; contract DESIGN.md §4.9, restated in tests/pngdec_restatement.py: the result
  * equals utils.io_utils.imread on every byte).  The host parses the chunks (cartoonsegmentation_amd/pngread.py) and hands over one
  * blob of device bytes and one descriptor per file; files of different sizes and colour types share a call.  8 bits per sample,

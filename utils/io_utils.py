@@ -30,7 +30,7 @@ def imread(path):
         return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
 
 
-def imread_device_many(paths, device=None, stats=None):
+def imread_device_many(paths, device=None, stats=None, progressive=None):
     """imread for a list of paths with the pixels on the device: a list of uint8 BGR [H,W,3] tensors.  A .jpg / .jpeg file that the
     device decoder takes (cartoonsegmentation_amd.jpegcode.probe: baseline, Huffman, grey or Y Cb Cr at 4:4:4 / 4:2:2 / 4:2:0) and
     whose EXIF orientation is 1 or absent is decoded on the MI355X by ops.jpeg_decode, all such files in one call: only the file's
@@ -38,9 +38,17 @@ def imread_device_many(paths, device=None, stats=None):
     grey + alpha or RGBA; not interlaced, not animated, no orientation) is decoded by ops.png_decode, again all such files in one
     call.  Every other file (BMP, progressive or rotated JPEG, 16-bit or interlaced PNG, ...) goes through imread and an upload.
     The device decodes follow the contracts of DESIGN.md §4.8 (JPEG) and §4.9 (PNG: equal to imread on every byte).  `stats` (a
-    dict) receives 'jpeg', 'png' and 'host': the indices of the paths that took each route."""
+    dict) receives 'jpeg', 'png' and 'host': the indices of the paths that took each route.
+
+    progressive=True (None reads the environment variable CSM_DEVICE_DECODE_PROGRESSIVE, '1' = on; the default is off) also sends
+    the progressive .jpg / .jpeg files that jpegcode.probe(data, progressive=True) accepts and whose orientation is 1 or absent to
+    the device, in the same ops.jpeg_decode call as the baseline ones; rotated progressive files and scan scripts
+    that the probe refuses stay with imread.  `stats` then also receives 'jpeg_progressive', the indices of those files, which are
+    listed in 'jpeg' as well."""
     import torch
     from cartoonsegmentation_amd import jpegcode, ops, pngread
+    if progressive is None:
+        progressive = os.environ.get('CSM_DEVICE_DECODE_PROGRESSIVE', '0') == '1'
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     out = [None] * len(paths)
     idx, datas, infos = [], [], []
@@ -52,7 +60,7 @@ def imread_device_many(paths, device=None, stats=None):
             with open(path, 'rb') as f:
                 data = f.read()
             try:
-                info = jpegcode.probe(data)
+                info = jpegcode.probe(data, progressive=True) if progressive else jpegcode.probe(data)
             except jpegcode.Unsupported:
                 info = None
             if info is not None and info['orientation'] in (None, 1):
@@ -71,19 +79,21 @@ def imread_device_many(paths, device=None, stats=None):
         host.append(i)
         out[i] = torch.from_numpy(imread(path)).to(dev)
     if datas:
-        for i, t in zip(idx, ops.jpeg_decode(datas, dev, _infos=infos)):
+        for i, t in zip(idx, ops.jpeg_decode(datas, dev, _infos=infos, progressive=bool(progressive))):
             out[i] = t
     if pdatas:
         for i, t in zip(pidx, ops.png_decode(pdatas, dev, _infos=pinfos)):
             out[i] = t
     if stats is not None:
         stats.update(jpeg=idx, png=pidx, host=host)
+        if progressive:
+            stats['jpeg_progressive'] = [i for i, info in zip(idx, infos) if info['progressive']]
     return out
 
 
-def imread_device(path, device=None):
+def imread_device(path, device=None, progressive=None):
     """imread with the pixels on the device: see imread_device_many"""
-    return imread_device_many([path], device)[0]
+    return imread_device_many([path], device, progressive=progressive)[0]
 
 
 def imwrite(img, file_path, auto_mkdir=True):
