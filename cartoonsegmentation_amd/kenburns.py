@@ -854,9 +854,12 @@ def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False
 
     A path ending in .gif (any letter case) is written as an animated GIF the same way: one 256-colour palette for the clip, an
     ordered dither and the LZW coding on the device (ops.gif_quantize, ops.gif_streams), the container by video.write_gif;
-    `quality` and `subsampling` do not apply."""
+    `quality` and `subsampling` do not apply.
+
+    A path ending in .webp (any letter case) is written as an animated WebP the same way: every frame one VP8 key frame, coded on
+    the device (ops.webp_streams with `quality`), the container by video.write_webp; `subsampling` does not apply."""
     suffix = str(video_save_path).lower()
-    if suffix.endswith('.avi') or suffix.endswith('.apng') or suffix.endswith('.gif'):
+    if suffix.endswith('.avi') or suffix.endswith('.apng') or suffix.endswith('.gif') or suffix.endswith('.webp'):
         from . import video
         if isinstance(npy_frame_list, torch.Tensor):
             frames = npy_frame_list
@@ -874,6 +877,11 @@ def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False
             streams, W, H = ops.gif_streams(indices)
             order = video.playback_order(len(streams)) if playback else None
             video.write_gif(video_save_path, streams, W, H, palette, fps=25, order=order)
+            return
+        if suffix.endswith('.webp'):
+            streams, W, H = ops.webp_streams(frames, quality=quality)
+            order = video.playback_order(len(streams)) if playback else None
+            video.write_webp(video_save_path, streams, W, H, fps=25, order=order)
             return
         jpegs = ops.jpeg_encode(frames, quality=quality, subsampling=subsampling)
         order = video.playback_order(len(jpegs)) if playback else None

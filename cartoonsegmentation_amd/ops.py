@@ -1023,6 +1023,70 @@ def png_encode(images, bgr=True):
     return [pngcode.png_file(s, W, H, colour_type) for s in streams]
 
 
+# ---- WebP of device frames (csrc/webp.hip + webpcode.py; video.write_webp, npyframes2video's .webp route) -------------------
+WEBP_SCRATCH_BYTES = 512 << 20         # frames are coded in chunks whose scratch stays below this (one frame is always taken)
+
+
+def webp_streams(frames, quality=90):
+    """The VP8 key frame (contract DESIGN.md §4.12) of every frame of the device uint8 frames [n,H,W,3] (or one [H,W,3]) in B, G, R
+    order, one `bytes` per frame: returns (streams, width, height).  quality 1..100 picks the frame's one quantiser index.  Colour
+    conversion, prediction, transforms and the boolean coder run on the device (csm_webp_measure / _write) in chunks of frames whose
+    scratch stays below WEBP_SCRATCH_BYTES; per chunk the host reads the size table once, then only the compressed bytes, and puts
+    the frame header and the partition sizes around them (webpcode.vp8_frame).
+
+    The format bounds what a frame may need, and only the coded sizes tell: the first partition (modes and skip flags, typically
+    under 1 byte per macroblock, 6.2 at the very worst) must stay below 2^19 bytes and a token partition below 2^24.  Frames of
+    1024 x 1024 at quality 90 stay below 1 % of either; a frame of several thousand pixels a side, or a very noisy one at a high
+    quality, can exceed it and then raises ValueError after the chunk's measure call, before any bytes are copied."""
+    from . import webpcode
+    quality = webpcode.check_quality(quality, "webp_streams")
+    if not isinstance(frames, torch.Tensor):
+        raise _lib.CsmError("webp_streams: frames must be a device tensor (got %s)" % type(frames).__name__)
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise _lib.CsmError("webp_streams: uint8 frames [n,H,W,3] or [H,W,3] expected (got %s %s)" % (frames.dtype, tuple(frames.shape)))
+    H, W = (int(v) for v in frames.shape[-3:-1])
+    webpcode.check_size(W, H, "webp_streams")
+    if not frames.is_cuda:
+        raise _lib.CsmError("webp_streams: frames must be a device tensor; libcsm355 has no CPU path")
+    fr = frames.contiguous()                                # named: alive until the kernels that read it are enqueued
+    if fr.dim() == 3:
+        fr = fr.unsqueeze(0)
+    n = int(fr.shape[0])
+    L, dev, st = _lib.load(), fr.device, stream_ptr(fr.device)
+    q, units = i32(quality), webpcode.partitions(H) + 1
+    per_frame = L.csm_webp_scratch_bytes(i32(1), i32(H), i32(W))
+    step = max(1, min(WEBP_SCRATCH_BYTES // per_frame, (2 ** 20 - 1) // units))
+    out = []
+    for f0 in range(0, n, step):
+        part = fr[f0:f0 + step]
+        k = int(part.shape[0])
+        info = torch.empty((k * units + 1, 2), dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.csm_webp_scratch_bytes(i32(k), i32(H), i32(W)), dtype=torch.uint8, device=dev)
+        check(L.csm_webp_measure(ptr(part), i32(k), i32(H), i32(W), q, ptr(info), ptr(scratch), st), "webp_measure")
+        info_h = info.cpu().numpy()                         # the one sync before the blob is sized
+        status, total = int(info_h[-1, 0]), int(info_h[-1, 1])
+        if status:
+            raise _lib.CsmError("webp_streams: a partition met the end of its scratch segment (status %d)" % status)
+        sizes = info_h[:-1, 1].reshape(k, units)            # refuse what the frame header cannot hold before the blob is made
+        if int(sizes[:, 0].max()) >= webpcode.MAX_FIRST_BYTES or int(sizes[:, 1:].max()) >= webpcode.MAX_PART_BYTES:
+            raise ValueError("webp_streams: a %dx%d frame at quality %d needs a first partition of %d bytes (limit %d) and a token "
+                             "partition of %d (limit %d)" % (W, H, quality, int(sizes[:, 0].max()), webpcode.MAX_FIRST_BYTES - 1,
+                                                             int(sizes[:, 1:].max()), webpcode.MAX_PART_BYTES - 1))
+        blob = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        check(L.csm_webp_write(i32(k), i32(H), i32(W), ptr(blob), i64(total), ptr(scratch), st), "webp_write")
+        host = blob.cpu().numpy().tobytes()
+        pieces = [host[o:o + b] for o, b in info_h[:-1].tolist()]
+        out += [webpcode.vp8_frame(pieces[j * units], pieces[j * units + 1:(j + 1) * units], W, H) for j in range(k)]
+    return out, W, H
+
+
+def webp_encode(frames, quality=90):
+    """Still WebP files (lossy, one VP8 key frame each; contract DESIGN.md §4.12) of device uint8 frames [n,H,W,3] (or one [H,W,3])
+    in B, G, R order: a list of n `bytes`, each a complete .webp file (webp_streams, then webpcode.still_file)."""
+    from . import webpcode
+    return [webpcode.still_file(s) for s in webp_streams(frames, quality=quality)[0]]
+
+
 # ---- GIF of device frames (csrc/gif.hip + gifcode.py; video.write_gif, npyframes2video's .gif route) ----------------------
 GIF_SCRATCH_BYTES = 64 << 20           # frames are coded in chunks whose scratch stays below this (one frame is always taken)
 

@@ -1,5 +1,5 @@
-"""Motion-JPEG AVI container, animated-PNG container and animated-GIF file (pure host code): the video files of the Ken Burns path,
-from frames that ops.jpeg_encode / ops.png_streams / ops.gif_streams compressed on the device.
+"""Motion-JPEG AVI container, animated-PNG container, animated-GIF and animated-WebP file (pure host code): the video files of the
+Ken Burns path, from frames that ops.jpeg_encode / ops.png_streams / ops.gif_streams / ops.webp_streams compressed on the device.
 
 A classic RIFF AVI (AVI 1.0, no OpenDML extension, so below 2 GiB):
 
@@ -20,7 +20,8 @@ An APNG (APNG specification 1.0) is a PNG whose first frame is the default image
     fcTL, fdAT <sequence number + zlib stream> ...      per further output frame; sequence numbers count fcTL and fdAT together
     IEND
 
-An animated GIF (GIF89a) is laid out by gifcode.gif_file.
+An animated GIF (GIF89a) is laid out by gifcode.gif_file, an animated WebP by webpcode.animation_file
+(DESIGN.md §4.12).
 """
 import struct
 
@@ -120,6 +121,17 @@ def write_gif(path, streams, width, height, palette, fps=25, loop=0, order=None)
     written."""
     from .gifcode import gif_file
     data = gif_file(streams, width, height, palette, fps=fps, loop=loop, order=order)
+    with open(path, 'wb') as f:
+        f.write(data)
+    return len(data)
+
+
+def write_webp(path, streams, width, height, fps=25, loop=0, order=None):
+    """Write the VP8 key frames `streams` (a list of bytes from ops.webp_streams, all width x height) as an animated WebP that
+    shows every frame for round(1000 / fps) ms and repeats `loop` times (0: for ever).  `order` as in write_mjpeg_avi: a frame is
+    coded once and may be written several times.  Returns the number of bytes written."""
+    from .webpcode import animation_file
+    data = animation_file(streams, width, height, fps=fps, loop=loop, order=order)
     with open(path, 'wb') as f:
         f.write(data)
     return len(data)

@@ -652,6 +652,26 @@ int csm_gif_map(const uint8_t *frames, int n, int H, int W, int flags, const uin
 int csm_gif_measure(const uint8_t *indices, int n, int H, int W, int64_t *bytes, void *scratch, void *stream);
 int csm_gif_write(int n, int H, int W, uint8_t *out, int64_t out_bytes, void *scratch, void *stream);
 
+/* The device half of a WebP file (webp.hip; contract DESIGN.md §4.12, restated in tests/webp_restatement.py, byte-identical):
+ * every frame as one VP8 key frame.  frames u8 [n,H,W,3] in B, G, R order, contiguous; 1 <= H, W <= 16383; quality 1..100;
+ * n * (partitions + 1) < 2^20, partitions = min(8, the largest power of two not above the macroblock rows).
+ * csm_webp_measure: colour conversion, the macroblock pass (one workgroup per frame) and the boolean coder (one lane per
+ *   partition) into scratch.  info device int64 [n * (partitions + 1) + 1][2]: per frame the (offset in the blob, bytes) of its
+ *   first partition and then of each token partition, in order; the last row is (status, total bytes), status != 0 if a partition
+ *   met the end of its scratch segment (the segments are sized so that it cannot).  scratch: csm_webp_scratch_bytes(n, H, W)
+ *   device bytes (0 for an invalid shape), shared with the write call: per macroblock 768 B of planes, 805 B of levels, modes and
+ *   flags, and 6 672 B of token segment (7 bits for each of the 25 * 305 pairs a macroblock can code), plus the first partitions.
+ * csm_webp_stage: one stage of csm_webp_measure alone, for timing (tools/time_webp.py): 1 colour, 2 macroblocks, 3 coder,
+ *   4 sizes; csm_webp_measure is the four in order.
+ * csm_webp_write: out: out_bytes device bytes; every partition's bytes at its offset, back to back.  Nothing is written past
+ *   out_bytes.  Same n, H, W and scratch as the measure call.
+ * The host adds the 10-byte frame header, the partition sizes and the RIFF chunks (webpcode.py).  Async on the stream, no
+ * allocation, no sync, integer arithmetic only: the output is deterministic. */
+size_t csm_webp_scratch_bytes(int n, int H, int W);
+int csm_webp_stage(int stage, const uint8_t *frames, int n, int H, int W, int quality, int64_t *info, void *scratch, void *stream);
+int csm_webp_measure(const uint8_t *frames, int n, int H, int W, int quality, int64_t *info, void *scratch, void *stream);
+int csm_webp_write(int n, int H, int W, uint8_t *out, int64_t out_bytes, void *scratch, void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */
