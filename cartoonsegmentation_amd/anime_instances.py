@@ -108,12 +108,15 @@ class AnimeInstances:
             return
         oh, ow = int(self.masks.shape[1]), int(self.masks.shape[2])
         hs, ws = h / oh, w / ow
-        bboxes = self.bboxes.float()
-        bboxes[:, ::2] *= hs
-        bboxes[:, 1::2] *= ws
-        self.bboxes = torch.round(bboxes).int()
+        if (oh, ow) != (h, w) or self.bboxes.dtype != torch.int32:
+            # (identity resize of int32 boxes: round(float(x) * 1.0) of an int32 below 2^24 is x -- they stay as they are)
+            bboxes = self.bboxes.float()
+            bboxes[:, ::2] *= hs
+            bboxes[:, 1::2] *= ws
+            self.bboxes = torch.round(bboxes).int()
         if (oh, ow) == (h, w):        # identity resize: interpolate(area) of a 0/1 mask then > 0.3 returns the mask itself
-            self.masks = self.masks.to(torch.float) > 0.3
+            if self.masks.dtype != torch.bool:                        # (a bool mask is already that result: no copy)
+                self.masks = self.masks.to(torch.float) > 0.3
         elif self.masks.is_cuda and mode == 'area' and self.masks.dtype == torch.bool:
             # device instances (the pipeline's case): adaptive-average resize + threshold in one hand-written pass over the 1-B masks
             from . import _lib

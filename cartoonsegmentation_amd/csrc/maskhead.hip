@@ -30,9 +30,14 @@ __device__ __forceinline__ void src_index(int dst, int in_size, int out_size, fl
 // ---- NMS ------------------------------------------------------------------------------------
 // boxes sorted by descending score.  mask[i][w] bit j: box (64w+j) is suppressed by box i (j > i).
 // mmcv devIoU: suppress iff inter > thr * (Sa + Sb - inter), box width = x2 - x1 (offset 0).
+// The image is grid dimension z: image b reads boxes[b][n][4] / cls_off[b][n] and owns mask + b * img_words (its scratch slice).
 __global__ __launch_bounds__(64) void k_nms_mask(const float *__restrict__ boxes, const float *__restrict__ cls_off,
-                                                  int n, float thr, unsigned long long *__restrict__ mask, int words) {
+                                                  int n, float thr, unsigned long long *__restrict__ mask, int words,
+                                                  int64_t img_words) {
     int i = blockIdx.x, w = blockIdx.y, j = w * 64 + threadIdx.x;
+    boxes += (int64_t)blockIdx.z * n * 4;
+    if (cls_off) cls_off += (int64_t)blockIdx.z * n;
+    mask += (int64_t)blockIdx.z * img_words;
     float ax1 = boxes[i * 4], ay1 = boxes[i * 4 + 1], ax2 = boxes[i * 4 + 2], ay2 = boxes[i * 4 + 3];
     float ao = cls_off ? cls_off[i] : 0.0f;
     ax1 += ao; ay1 += ao; ax2 += ao; ay2 += ao;
@@ -50,9 +55,13 @@ __global__ __launch_bounds__(64) void k_nms_mask(const float *__restrict__ boxes
     if (threadIdx.x == 0) mask[(int64_t)i * words + w] = b;
 }
 
-// one wave scans the boxes in score order; lane w owns word w of the removed-set (n <= 4096)
+// one wave per image scans its boxes in score order; lane w owns word w of the removed-set (n <= 4096)
 __global__ __launch_bounds__(64) void k_nms_scan(const unsigned long long *__restrict__ mask, int n, int words,
-                                                  int *__restrict__ keep, int *__restrict__ n_keep, int max_keep) {
+                                                  int *__restrict__ keep, int *__restrict__ n_keep, int max_keep,
+                                                  int64_t img_words) {
+    mask += (int64_t)blockIdx.x * img_words;
+    keep += (int64_t)blockIdx.x * max_keep;
+    n_keep += blockIdx.x;
     unsigned long long removed = 0ull;
     int lane = threadIdx.x, cnt = 0;
     for (int i = 0; i < n && cnt < max_keep; ++i) {   // results[:max_per_img]: later boxes cannot change earlier keeps
@@ -70,14 +79,32 @@ __global__ __launch_bounds__(64) void k_nms_scan(const unsigned long long *__res
 // ---- dynamic-conv mask head ------------------------------------------------------------------
 // per instance: x = [rel_x, rel_y, mask_feat(P)] -> (P+2 -> D) relu -> (D -> D) relu -> (D -> 1)
 // params [n, G] laid out as mmdet parse_dynamic_params: weights [ (P+2)*D | D*D | D ] then biases [ D | D | 1 ].
+// The launch covers the first n_k detections of up to kDetChunk frames as ONE flat instance list (grid dimension y): frame f owns the
+// flat indices [start[f], start[f + 1]), its prototype map starts at feat + f * feat_frame and its detections sit in slots
+// [f * slots, f * slots + n_k) of params / priors / boxes.  The table travels by value in the kernel arguments.  The single-image
+// entry point is the one-frame case.  With boxes_out the block of an instance's first pixels also writes its box as int32 xywh
+// (`boxes.to(int32)`, then `wh -= xy`: AnimeInsSeg._instances_from).
+constexpr int kDetChunk = 16;
+struct DetFrames { int start[kDetChunk + 1]; int nf; };
+
 template <int P, int D>
-__global__ __launch_bounds__(256) void k_maskhead(const float *__restrict__ feat, int ld, int h, int w,
+__global__ __launch_bounds__(256) void k_maskhead(const float *__restrict__ feat, int64_t feat_frame, int ld, int h, int w,
                                                    const float *__restrict__ params, int G,
-                                                   const float *__restrict__ priors, int feat_stride,
-                                                   float *__restrict__ logits) {
+                                                   const float *__restrict__ priors, int slots, int feat_stride,
+                                                   float *__restrict__ logits, const float *__restrict__ boxes,
+                                                   int *__restrict__ boxes_out, DetFrames FR) {
     __shared__ float sp[(P + 2) * D + D * D + D + D + D + 1];
-    const int inst = blockIdx.y;
-    for (int i = threadIdx.x; i < G; i += 256) sp[i] = params[(int64_t)inst * G + i];
+    const int flat = blockIdx.y;
+    int f = 0;
+    while (f + 1 < FR.nf && flat >= FR.start[f + 1]) ++f;
+    const int64_t inst = (int64_t)f * slots + (flat - FR.start[f]);
+    feat += (int64_t)f * feat_frame;
+    for (int i = threadIdx.x; i < G; i += 256) sp[i] = params[inst * G + i];
+    if (boxes_out && blockIdx.x == 0 && threadIdx.x < 4) {
+        const int t = threadIdx.x;
+        const unsigned v = (unsigned)(int)boxes[inst * 4 + t];
+        boxes_out[(int64_t)flat * 4 + t] = (int)(t < 2 ? v : v - (unsigned)(int)boxes[inst * 4 + t - 2]);
+    }
     __syncthreads();
     int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= h * w) return;
@@ -111,7 +138,7 @@ __global__ __launch_bounds__(256) void k_maskhead(const float *__restrict__ feat
     float a = b2[0];
 #pragma unroll
     for (int c = 0; c < D; ++c) a = fmaf(h1[c], w2[c], a);
-    logits[(int64_t)inst * h * w + pix] = a;
+    logits[(int64_t)flat * h * w + pix] = a;
 }
 
 __device__ __forceinline__ float bilerp(const float *__restrict__ L, int w, int y0, int y1, int x0, int x1, float hl0,
@@ -182,11 +209,16 @@ __global__ __launch_bounds__(256) void k_refine_threshold(const float *__restric
 // out: [n,4,T,T] NCHW fp32.  rh, rw = resized size (<= T).  uint8 path = cv2's 11-bit fixed point.
 // The mask plane has its OWN size (Hm,Wm) and resized extent (rhm,rwm): mmdet's `[..., :ori_h, :ori_w]` slice can leave the
 // detector masks 1-2 px smaller than the image, and the reference resize_pad()s each seg by its own shape.
-__global__ __launch_bounds__(256) void k_refine_batch(const uint8_t *__restrict__ img, const uint8_t *__restrict__ masks,
-                                                       int H, int W, int rh, int rw, int Hm, int Wm, int rhm, int rwm, int T,
-                                                       float *__restrict__ out) {
+// Item i of a launch (grid dimension z, at most kRefineChunk) names its own image and its own single mask plane: the two pointer
+// tables travel by value in the kernel arguments.
+constexpr int kRefineChunk = 16;
+struct RefineItems { const uint8_t *img[kRefineChunk]; const uint8_t *mask[kRefineChunk]; };
+
+__global__ __launch_bounds__(256) void k_refine_batch(RefineItems R, int H, int W, int rh, int rw, int Hm, int Wm, int rhm,
+                                                       int rwm, int T, float *__restrict__ out) {
     const int inst = blockIdx.z, y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x;
     if (x >= T) return;
+    const uint8_t *__restrict__ img = R.img[inst];
     float *O = out + (int64_t)inst * 4 * T * T + (int64_t)y * T + x;
     const int64_t plane = (int64_t)T * T;
     if (y >= rh || x >= rw) { O[0] = 0.0f; O[plane] = 0.0f; O[2 * plane] = 0.0f; }
@@ -207,7 +239,7 @@ __global__ __launch_bounds__(256) void k_refine_batch(const uint8_t *__restrict_
             O[c * plane] = (float)v / 255.0f;
         }
     }
-    const uint8_t *M = masks + (int64_t)inst * Hm * Wm;
+    const uint8_t *__restrict__ M = R.mask[inst];
     if (y >= rhm || x >= rwm) { O[3 * plane] = 0.0f; return; }
     if (rhm == Hm && rwm == Wm) { O[3 * plane] = (float)M[(int64_t)y * Wm + x]; return; }
     // float32 path: plain fp32 bilinear
@@ -284,9 +316,29 @@ extern "C" int csm_nms(const float *boxes, const float *class_offsets, int n, fl
     CSM_REQUIRE(boxes && scratch);
     int words = (n + 63) / 64;
     unsigned long long *mask = (unsigned long long *)scratch;
-    k_nms_mask<<<dim3(n, words), 64, 0, st>>>(boxes, class_offsets, n, iou_thr, mask, words);
+    k_nms_mask<<<dim3(n, words), 64, 0, st>>>(boxes, class_offsets, n, iou_thr, mask, words, 0);
     int rc = csm::check_launch("k_nms_mask"); if (rc) return rc;
-    k_nms_scan<<<1, 64, 0, st>>>(mask, n, words, keep, n_keep, max_keep);
+    k_nms_scan<<<1, 64, 0, st>>>(mask, n, words, keep, n_keep, max_keep, 0);
+    return csm::check_launch("k_nms_scan");
+}
+
+extern "C" size_t csm_nms_batch_scratch_bytes(int nb, int n) {
+    if (nb <= 0 || n < 0) return 0;
+    return (size_t)nb * csm_nms_scratch_bytes(n);
+}
+
+extern "C" int csm_nms_batch(const float *boxes, const float *class_offsets, int nb, int n, float iou_thr, int max_keep, int *keep,
+                             int *n_keep, void *scratch, void *stream) {
+    CSM_REQUIRE(keep && n_keep && nb > 0 && nb <= 65535 && n >= 0 && n <= 4096 && max_keep > 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { CSM_HIP(hipMemsetAsync(n_keep, 0, (size_t)nb * sizeof(int), st)); return CSM_OK; }
+    CSM_REQUIRE(boxes && scratch && !(((uintptr_t)scratch) & 7));
+    const int words = (n + 63) / 64;
+    const int64_t img_words = (int64_t)(csm_nms_scratch_bytes(n) / 8);          // every image its own slice of the scratch
+    unsigned long long *mask = (unsigned long long *)scratch;
+    k_nms_mask<<<dim3(n, words, nb), 64, 0, st>>>(boxes, class_offsets, n, iou_thr, mask, words, img_words);
+    int rc = csm::check_launch("k_nms_mask"); if (rc) return rc;
+    k_nms_scan<<<nb, 64, 0, st>>>(mask, n, words, keep, n_keep, max_keep, img_words);
     return csm::check_launch("k_nms_scan");
 }
 
@@ -297,8 +349,11 @@ extern "C" int csm_maskhead_logits(const float *mask_feat, int ld, int h, int w,
     if (n == 0) return CSM_OK;
     CSM_REQUIRE(kernels && priors);
     if (num_prototypes != 8 || dyconv_channels != 8) return csm::fail_arg("mask head compiled for 8 prototypes x 8 dyconv channels");
+    CSM_REQUIRE(n <= 65535);
+    DetFrames F{};
+    F.nf = 1; F.start[1] = n;
     k_maskhead<8, 8><<<dim3(csm::cdiv((int64_t)h * w, 256), n), 256, 0, (hipStream_t)stream>>>(
-        mask_feat, ld, h, w, kernels, 169, priors, feat_stride, logits);
+        mask_feat, 0, ld, h, w, kernels, 169, priors, n, feat_stride, logits, nullptr, nullptr, F);
     return csm::check_launch("k_maskhead");
 }
 
@@ -314,13 +369,75 @@ extern "C" int csm_mask_resize_threshold(const float *logits, int n, int h, int 
     return csm::check_launch("k_mask_resize_threshold");
 }
 
+extern "C" int csm_det_masks_batch(const float *mask_feat, int64_t sample_stride, int ld, int h, int w, int num_prototypes,
+                                   int dyconv_channels, const float *kernels, const float *priors, const float *boxes, int nb,
+                                   int max_keep, const int *n_k, int feat_stride, int up, int rh, int rw, int oh, int ow, float thr,
+                                   float *logits, uint8_t *masks, int *boxes_xywh, void *stream) {
+    CSM_REQUIRE(nb > 0 && n_k && max_keep > 0 && h > 0 && w > 0 && ld >= num_prototypes && sample_stride >= 0);
+    CSM_REQUIRE(up > 0 && rh >= oh && rw >= ow && oh > 0 && ow > 0);
+    if (num_prototypes != 8 || dyconv_channels != 8) return csm::fail_arg("mask head compiled for 8 prototypes x 8 dyconv channels");
+    int64_t total = 0;
+    for (int k = 0; k < nb; ++k) { CSM_REQUIRE(n_k[k] >= 0 && n_k[k] <= max_keep); total += n_k[k]; }
+    if (total == 0) return CSM_OK;
+    CSM_REQUIRE(total <= 65535 && mask_feat && kernels && priors && boxes && logits && masks && boxes_xywh);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t hw = (int64_t)h * w;
+    int done = 0;
+    for (int f0 = 0; f0 < nb; f0 += kDetChunk) {                            // one launch per kDetChunk frames
+        DetFrames F{};
+        F.nf = nb - f0 < kDetChunk ? nb - f0 : kDetChunk;
+        for (int k = 0; k < F.nf; ++k) F.start[k + 1] = F.start[k] + n_k[f0 + k];
+        const int n = F.start[F.nf];
+        if (n == 0) continue;
+        k_maskhead<8, 8><<<dim3(csm::cdiv(hw, 256), n), 256, 0, st>>>(
+            mask_feat + (int64_t)f0 * sample_stride, sample_stride, ld, h, w, kernels + (int64_t)f0 * max_keep * 169, 169,
+            priors + (int64_t)f0 * max_keep * 4, max_keep, feat_stride, logits + (int64_t)done * hw,
+            boxes + (int64_t)f0 * max_keep * 4, boxes_xywh + (int64_t)done * 4, F);
+        int rc = csm::check_launch("k_maskhead"); if (rc) return rc;
+        done += n;
+    }
+    // the tail works on the flat [sum n_k, h, w] logits as it does on one frame's
+    k_mask_resize_threshold<<<dim3(csm::cdiv((ow + 3) / 4, 256), oh, (int)total), 256, 0, st>>>(logits, h, w, up, rh, rw, oh, ow,
+                                                                                                 thr, masks);
+    return csm::check_launch("k_mask_resize_threshold");
+}
+
+namespace {
+int refine_prepare_launch(const uint8_t *const *imgs, const uint8_t *const *masks, int n, int H, int W, int rh, int rw, int Hm,
+                          int Wm, int rhm, int rwm, int T, float *batch, hipStream_t st) {
+    for (int i0 = 0; i0 < n; i0 += kRefineChunk) {                          // one launch per kRefineChunk items
+        RefineItems R{};
+        const int ni = n - i0 < kRefineChunk ? n - i0 : kRefineChunk;
+        for (int i = 0; i < ni; ++i) { R.img[i] = imgs[i0 + i]; R.mask[i] = masks[i0 + i]; }
+        k_refine_batch<<<dim3(csm::cdiv(T, 256), T, ni), 256, 0, st>>>(R, H, W, rh, rw, Hm, Wm, rhm, rwm, T,
+                                                                        batch + (int64_t)i0 * 4 * T * T);
+        int rc = csm::check_launch("k_refine_batch"); if (rc) return rc;
+    }
+    return CSM_OK;
+}
+}  // namespace
+
 extern "C" int csm_refine_prepare_batch(const uint8_t *img_hwc, const uint8_t *masks, int n, int H, int W, int rh, int rw,
                                         int Hm, int Wm, int rhm, int rwm, int T, float *batch, void *stream) {
     CSM_REQUIRE(img_hwc && masks && batch && n > 0 && H > 0 && W > 0 && rh <= T && rw <= T);
     CSM_REQUIRE(Hm > 0 && Wm > 0 && rhm > 0 && rwm > 0 && rhm <= T && rwm <= T && rh > 0 && rw > 0);
-    k_refine_batch<<<dim3(csm::cdiv(T, 256), T, n), 256, 0, (hipStream_t)stream>>>(img_hwc, masks, H, W, rh, rw, Hm, Wm, rhm,
-                                                                                     rwm, T, batch);
-    return csm::check_launch("k_refine_batch");
+    for (int i0 = 0; i0 < n; i0 += kRefineChunk) {
+        const uint8_t *ip[kRefineChunk], *mp[kRefineChunk];
+        const int ni = n - i0 < kRefineChunk ? n - i0 : kRefineChunk;
+        for (int i = 0; i < ni; ++i) { ip[i] = img_hwc; mp[i] = masks + (int64_t)(i0 + i) * Hm * Wm; }
+        int rc = refine_prepare_launch(ip, mp, ni, H, W, rh, rw, Hm, Wm, rhm, rwm, T, batch + (int64_t)i0 * 4 * T * T,
+                                       (hipStream_t)stream);
+        if (rc) return rc;
+    }
+    return CSM_OK;
+}
+
+extern "C" int csm_refine_prepare_many(const uint8_t *const *imgs_hwc, const uint8_t *const *masks, int n, int H, int W, int rh,
+                                       int rw, int Hm, int Wm, int rhm, int rwm, int T, float *batch, void *stream) {
+    CSM_REQUIRE(imgs_hwc && masks && batch && n > 0 && H > 0 && W > 0 && rh <= T && rw <= T);
+    CSM_REQUIRE(Hm > 0 && Wm > 0 && rhm > 0 && rwm > 0 && rhm <= T && rwm <= T && rh > 0 && rw > 0);
+    for (int i = 0; i < n; ++i) CSM_REQUIRE(imgs_hwc[i] && masks[i]);
+    return refine_prepare_launch(imgs_hwc, masks, n, H, W, rh, rw, Hm, Wm, rhm, rwm, T, batch, (hipStream_t)stream);
 }
 
 extern "C" int csm_refine_threshold(const float *logits, int n, int S_h, int S_w, int crop_h, int crop_w, int oh, int ow,

@@ -5,6 +5,8 @@ Flow per image (reference :464-504, :447-462, :638-665), everything on the MI355
   uint8 image --csm_det_preprocess--> RTMDet-Ins layer program --csm_det_decode--> csm_nms --csm_det_gather-->
   csm_maskhead_logits --> csm_mask_resize_threshold --> [ISNet refine: csm_refine_prepare_batch --> ISNet layer
   program --> csm_refine_threshold] --> AnimeInstances(masks bool [n,H,W], bboxes xywh int32, scores).
+Equally sized frames share one detector run and ISNet batches, and their glue runs once for all frames: csm_nms_batch,
+csm_det_masks_batch, csm_refine_prepare_many and one csm_refine_threshold per ISNet batch (CSM_SEG_GLUE_BATCH=0: item by item).
 refine_method='animeseg' (reference :78-115, :623-630) instead runs the anime-seg ISNet-IS over the frame:
   csm_animeseg_prepare --> ISNetDIS(in_ch=3) layer program --> csm_animeseg_mask (fg) --> csm_animeseg_select (in place).
 The reference makes 5 host<->device crossings per image; here the only syncs are the data-dependent counts.
@@ -168,6 +170,9 @@ class AnimeInsSeg:
         self.refine_method = None
         self.refine_batch = int(os.environ.get('CSM_REFINE_BATCH', '16'))   # instances per ISNet run when frames are batched
         self.det_batch = max(1, int(os.environ.get('CSM_DET_BATCH', '16')))  # frames per detector run (longer lists are chunked)
+        # the per-instance / per-frame glue of equally sized frames as a handful of native launches (csm_nms_batch, csm_det_masks_batch,
+        # csm_refine_prepare_many, one csm_refine_threshold per ISNet chunk); 0 = the per-item calls (same bits: the A/B switch)
+        self.seg_glue_batch = os.environ.get('CSM_SEG_GLUE_BATCH', '1') != '0'
         self.device_decode = os.environ.get('CSM_DEVICE_DECODE', '0') == '1'  # path inputs: baseline JPEG and 8-bit PNG files are decoded on the device
         self.set_refine_method(**(refine_kwargs or {'refine_method': 'none'}))
 
@@ -260,7 +265,10 @@ class AnimeInsSeg:
             imgs = self._load(imgs)
         same = len(imgs) > 1 and all(tuple(im.shape) == tuple(imgs[0].shape) for im in imgs)
         if same:            # equally sized frames: one batched detector run + refine batches shared across frames
-            insts = [self._instances_from(d, pred_score_thr) for d in self.detect_raw_batch(imgs)]
+            dets = self.detect_raw_batch(imgs)
+            insts = self._instances_from_run(dets, pred_score_thr) if self.seg_glue_batch else None
+            if insts is None:
+                insts = [self._instances_from(d, pred_score_thr) for d in dets]
             if self.refine_method == 'refinenet_isnet':
                 self._refine_many(list(zip(insts, imgs)), self.refine_size)
             elif self.refine_method == 'animeseg':
@@ -434,12 +442,21 @@ class AnimeInsSeg:
                                f32(rw), f32(rh), f32(sfx), f32(sfy), f32(cfg.min_bbox_size), i32(K), ptr(scores), ptr(boxes), ptr(src),
                                ptr(labels), ptr(offs), ptr(scratch), stream_ptr()), "det_decode")
         keep = torch.zeros((nb, M), dtype=torch.int32, device=dev)
-        nk = torch.zeros(nb, dtype=torch.int32, device=dev)
-        nscr = torch.empty(L.csm_nms_scratch_bytes(i32(K)), dtype=torch.uint8, device=dev)
-        for bi in range(nb):
-            check(L.csm_nms(ptr(boxes[bi]), ptr(None if offs is None else offs[bi]), i32(K), f32(cfg.nms_iou), i32(M),
-                            ptr(keep[bi]), ptr(nk[bi:bi + 1]), ptr(nscr), stream_ptr()), "nms")
-        k_scores = torch.empty((nb, M), dtype=torch.float32, device=dev)
+        batched = self.seg_glue_batch
+        if batched:
+            # kept scores and kept counts share one block, so the host gets both in ONE read: [nb * M] float32, then [nb] int32
+            read = torch.empty(nb * M + nb, dtype=torch.float32, device=dev)
+            k_scores, nk = read[:nb * M].view(nb, M), read[nb * M:].view(torch.int32)
+            nscr = torch.empty(L.csm_nms_batch_scratch_bytes(i32(nb), i32(K)), dtype=torch.uint8, device=dev)
+            check(L.csm_nms_batch(ptr(boxes), ptr(offs), i32(nb), i32(K), f32(cfg.nms_iou), i32(M), ptr(keep), ptr(nk), ptr(nscr),
+                                  stream_ptr()), "nms_batch")
+        else:
+            nk = torch.zeros(nb, dtype=torch.int32, device=dev)
+            nscr = torch.empty(L.csm_nms_scratch_bytes(i32(K)), dtype=torch.uint8, device=dev)
+            for bi in range(nb):
+                check(L.csm_nms(ptr(boxes[bi]), ptr(None if offs is None else offs[bi]), i32(K), f32(cfg.nms_iou), i32(M),
+                                ptr(keep[bi]), ptr(nk[bi:bi + 1]), ptr(nscr), stream_ptr()), "nms")
+            k_scores = torch.empty((nb, M), dtype=torch.float32, device=dev)
         k_boxes = torch.empty((nb, M, 4), dtype=torch.float32, device=dev)
         k_labels = torch.empty((nb, M), dtype=torch.int32, device=dev)
         k_priors = torch.empty((nb, M, 4), dtype=torch.float32, device=dev)
@@ -447,11 +464,16 @@ class AnimeInsSeg:
         check(L.csm_det_gather(ker_p, level_hw, strides, lds3, i32(nl), i32(nb), i32(K), i32(M), i32(G), ptr(keep), ptr(scores), ptr(boxes),
                                ptr(src), ptr(labels), ptr(k_scores), ptr(k_boxes), ptr(k_labels), ptr(k_priors), ptr(k_kernels),
                                stream_ptr()), "det_gather")
-        nk_h, ks_h = nk.tolist(), k_scores.tolist()                                # the one host sync of the decode
+        if batched:
+            host = read.cpu().numpy()                                              # the one host sync (and host read) of the decode
+            nk_h, ks_h = host[nb * M:].view(np.int32).tolist(), host[:nb * M].reshape(nb, M).tolist()
+        else:
+            nk_h, ks_h = nk.tolist(), k_scores.tolist()                            # the one host sync of the decode
+        run = dict(nb=nb, M=M, boxes=k_boxes, scores=k_scores, priors=k_priors, kernels=k_kernels)    # the run's [nb, M, ...] blocks
         outs = []
         for bi in range(nb):
             n = sum(1 for j in range(nk_h[bi]) if ks_h[bi][j] > cfg.score_thr)    # valid ones come first in keep[]
-            out = dict(H=H, W=W, S=S, rh=rh, rw=rw, w_scale=w_scale, h_scale=h_scale, rp=rp, cp=cp, bi=bi, n=n)
+            out = dict(H=H, W=W, S=S, rh=rh, rw=rw, w_scale=w_scale, h_scale=h_scale, rp=rp, cp=cp, bi=bi, n=n, run=run)
             if n:
                 out.update(boxes=k_boxes[bi, :n], scores=k_scores[bi, :n], priors=k_priors[bi, :n], kernels=k_kernels[bi, :n],
                            labels=k_labels[bi, :n], scores_host=ks_h[bi][:n])
@@ -511,6 +533,45 @@ class AnimeInsSeg:
         bboxes[:, 2:] -= bboxes[:, :2]
         return AnimeInstances(masks, bboxes, d['scores'][sel])
 
+    def _instances_from_run(self, dets, pred_score_thr: float = 0.3):
+        """_instances_from for all frames of ONE detector run in one native call (csm_det_masks_batch): every frame's masks are rows
+        of one uint8 [sum n_k, oh, ow] block (handed out as bool views: the kernel writes 0 / 1 only), its boxes rows of one int32
+        block, its scores a view of the run's kept scores.  The kept detections are in descending score order, so `> pred_score_thr`
+        selects a prefix, whose length comes from the host copy of the scores.  Returns None (the caller then goes frame by frame)
+        when the frames are not those of one run with the prototype maps still in the workspace, or a selection is not a prefix."""
+        L, cfg = _lib.load(), self.cfg
+        run = dets[0].get('run')
+        if run is None or len(dets) != run['nb'] or any(d.get('run') is not run or d['bi'] != k or 'mask_feat' in d for k, d in enumerate(dets)):
+            return None
+        n_k = []
+        for d in dets:
+            idx = [j for j, v in enumerate(d['scores_host']) if np.float32(v) > np.float32(pred_score_thr)] if d['n'] else []
+            if idx != list(range(len(idx))):
+                return None
+            n_k.append(len(idx))
+        total = sum(n_k)
+        if total == 0:
+            return [AnimeInstances() for _ in dets]
+        d0 = dets[0]
+        v = d0['rp'].mask_feat
+        b = v.buf
+        feat = d0['cp'].workspace[b.offset:]                       # sample k's map: v.h * v.w * b.c floats per sample further on
+        h, w, up = v.h, v.w, cfg.strides[0]
+        rh2 = math.ceil(h * up * (1 / d0['w_scale'])); rw2 = math.ceil(w * up * (1 / d0['h_scale']))      # as in _masks_from
+        oh, ow = min(rh2, d0['H']), min(rw2, d0['W'])
+        logits = torch.empty((total, h, w), dtype=torch.float32, device=self.device)
+        masks = torch.empty((total, oh, ow), dtype=torch.uint8, device=self.device)
+        bboxes = torch.empty((total, 4), dtype=torch.int32, device=self.device)
+        check(L.csm_det_masks_batch(ptr(feat), ctypes.c_int64(v.h * v.w * b.c), i32(b.c), i32(h), i32(w), i32(cfg.num_prototypes),
+                                    i32(cfg.dyconv_channels), ptr(run['kernels']), ptr(run['priors']), ptr(run['boxes']), i32(run['nb']),
+                                    i32(run['M']), (ctypes.c_int * len(n_k))(*n_k), i32(up), i32(up), i32(rh2), i32(rw2), i32(oh), i32(ow),
+                                    f32(cfg.mask_thr_binary), ptr(logits), ptr(masks), ptr(bboxes), stream_ptr()), "det_masks_batch")
+        insts, s = [], 0
+        for k, n in enumerate(n_k):
+            insts.append(AnimeInstances(masks[s:s + n].view(torch.bool), bboxes[s:s + n], run['scores'][k, :n]) if n else AnimeInstances())
+            s += n
+        return insts
+
     # ---- Web-UI helpers (reference :241-393): detector embeddings + box-prompted masks ---------------------
     def infer_embeddings(self, imgs, det_size=None):
         """reference :241-337: returns (img, instance_data, mask_feat) with the NMS'ed detections *before* mask
@@ -566,12 +627,17 @@ class AnimeInsSeg:
         """ISNet refine of several (instances, image) pairs of equal image size with shared batches (per-sample results are
         those of _postprocess_refine; the reference's per-image limit of 4 only bounds its memory use)."""
         L = _lib.load()
+        batched = self.seg_glue_batch
         jobs = []
         for inst, img in pairs:
             if inst.is_empty:
                 continue
             img_d = self._upload(img)
-            segs = inst.masks.to(self.device).to(torch.uint8).contiguous()
+            segs = inst.masks.to(self.device)
+            if batched and segs.dtype == torch.bool and segs.is_contiguous():
+                segs = segs.view(torch.uint8)                       # bool storage is 0 / 1 bytes: no copy
+            else:
+                segs = segs.to(torch.uint8).contiguous()
             jobs.append((inst, img_d, segs))
         if not jobs:
             return
@@ -581,8 +647,31 @@ class AnimeInsSeg:
         Hm, Wm = int(jobs[0][2].shape[1]), int(jobs[0][2].shape[2])       # equal image sizes => equal detector mask sizes
         rhm, rwm = scaledown_size(Hm, Wm, T)
         flat = [(j, k) for j, (_, _, segs) in enumerate(jobs) for k in range(segs.shape[0])]
-        outs = [torch.empty((segs.shape[0], H, W), dtype=torch.uint8, device=self.device) for _, _, segs in jobs]
         max_batch = max_batch or self.refine_batch
+        if batched:
+            # ONE output block for the step: `flat` is frame-major, so a chunk's outputs are consecutive rows and a frame's masks a
+            # row range; per ISNet chunk one prepare launch (pointer tables) and one threshold launch
+            block = torch.empty((len(flat), H, W), dtype=torch.uint8, device=self.device)
+            for c0 in range(0, len(flat), max_batch):
+                chunk = flat[c0:c0 + max_batch]
+                b = len(chunk)
+                cp = self._refiner(b, T)
+                batch = torch.empty((b, 4, T, T), dtype=torch.float32, device=self.device)
+                VP = ctypes.c_void_p * b
+                check(L.csm_refine_prepare_many(VP(*[jobs[j][1].data_ptr() for j, _ in chunk]),
+                                                VP(*[jobs[j][2].data_ptr() + k * Hm * Wm for j, k in chunk]), i32(b), i32(H), i32(W),
+                                                i32(rh), i32(rw), i32(Hm), i32(Wm), i32(rhm), i32(rwm), i32(T), ptr(batch), stream_ptr()),
+                      "refine_prepare_many")
+                logits = torch.empty((b, 1, T, T), dtype=torch.float32, device=self.device)
+                cp.run(batch, logits)
+                check(L.csm_refine_threshold(ptr(logits), i32(b), i32(T), i32(T), i32(rh), i32(rw), i32(H), i32(W),
+                                             f32(self.mask_thr), ptr(block[c0:c0 + b]), stream_ptr()), "refine_threshold")
+            s = 0
+            for inst, _, segs in jobs:
+                inst.masks = block[s:s + segs.shape[0]].view(torch.bool)
+                s += segs.shape[0]
+            return
+        outs = [torch.empty((segs.shape[0], H, W), dtype=torch.uint8, device=self.device) for _, _, segs in jobs]
         for c0 in range(0, len(flat), max_batch):
             chunk = flat[c0:c0 + max_batch]
             b = len(chunk)

@@ -428,6 +428,12 @@ int csm_det_gather(const float *const *kern, const int *level_hw, const int *str
 size_t csm_nms_scratch_bytes(int n);
 int csm_nms(const float *boxes, const float *class_offsets, int n, float iou_thr, int max_keep, int *keep,
             int *n_keep, void *scratch, void *stream);
+/* csm_nms for the nb images of a detector run in ONE call (two launches, whatever nb): boxes [nb][n][4], class_offsets [nb][n] or
+ * NULL, keep [nb][max_keep], n_keep [nb].  The image is a grid dimension of the same kernels; image b works in its own slice of
+ * scratch (csm_nms_batch_scratch_bytes(nb, n) bytes, 8-byte aligned) and gets exactly what csm_nms gives for it. */
+size_t csm_nms_batch_scratch_bytes(int nb, int n);
+int csm_nms_batch(const float *boxes, const float *class_offsets, int nb, int n, float iou_thr, int max_keep, int *keep,
+                  int *n_keep, void *scratch, void *stream);
 
 /* RTMDetInsSepBNHeadCustom._mask_predict_by_feat_single   animeinsseg/models/rtmdet_inshead_custom.py:253-303
  * mask_feat NHWC [h,w,num_prototypes] with channel pitch ld; kernels [n,169]; priors [n,4] = (x,y,stride,stride);
@@ -442,6 +448,18 @@ int csm_maskhead_logits(const float *mask_feat, int ld, int h, int w, int num_pr
  * (mmdet's ceil(S / scale) lands 1-2 px under the original size for ~20 % of image shapes). */
 int csm_mask_resize_threshold(const float *logits, int n, int h, int w, int up, int rh, int rw, int oh, int ow,
                               float thr, uint8_t *masks, void *stream);
+/* csm_maskhead_logits + csm_mask_resize_threshold for all nb frames of a detector run in ONE call (one mask-head launch per 16
+ * frames and one tail launch), plus the box conversion of AnimeInsSeg._instances_from.  Frame k contributes its first n_k[k]
+ * detections (n_k: HOST array of nb entries, read before the call returns, each 0 <= n_k[k] <= max_keep); the instances of all
+ * frames form one flat frame-major list of sum(n_k) entries.  mask_feat: frame 0's NHWC prototype map, frame k's starts
+ * sample_stride floats further on per frame (the detector workspace's sample stride); kernels [nb][max_keep][169], priors and boxes
+ * [nb][max_keep][4] as csm_det_gather wrote them (boxes xyxy float).  Outputs: logits [sum n_k][h][w] (scratch), masks uint8
+ * [sum n_k][oh][ow] (0/1) and boxes_xywh int32 [sum n_k][4] = (int)x1, (int)y1, (int)x2 - (int)x1, (int)y2 - (int)y1.  Entry by
+ * entry the bits of the per-frame pair of calls; nothing is written past sum(n_k) entries; sum(n_k) == 0 launches nothing. */
+int csm_det_masks_batch(const float *mask_feat, int64_t sample_stride, int ld, int h, int w, int num_prototypes,
+                        int dyconv_channels, const float *kernels, const float *priors, const float *boxes, int nb, int max_keep,
+                        const int *n_k, int feat_stride, int up, int rh, int rw, int oh, int ow, float thr, float *logits,
+                        uint8_t *masks, int *boxes_xywh, void *stream);
 
 /* prepare_refine_batch   animeinsseg/__init__.py:37-55 (+ utils/io_utils.py:254-292 resize_pad):
  * img u8 HWC [H,W,3], masks u8 [n,Hm,Wm] -> batch fp32 NCHW [n,4,T,T]; (rh,rw) = keep-ratio size of the image inside T x T,
@@ -449,6 +467,12 @@ int csm_mask_resize_threshold(const float *logits, int n, int h, int w, int up, 
  * masks can be 1-2 px smaller than the image, see csm_mask_resize_threshold). */
 int csm_refine_prepare_batch(const uint8_t *img_hwc, const uint8_t *masks, int n, int H, int W, int rh, int rw, int Hm, int Wm,
                              int rhm, int rwm, int T, float *batch, void *stream);
+/* csm_refine_prepare_batch for n items that each name their OWN image (imgs_hwc[i]: u8 HWC [H,W,3]) and their own single mask plane
+ * (masks[i]: u8 [Hm,Wm]) -> batch [n,4,T,T], one launch per 16 items.  imgs_hwc and masks are HOST arrays of n device pointers, read
+ * before the call returns and passed on by value in kernel arguments (no pointer table in device memory).  Item i gets exactly
+ * what csm_refine_prepare_batch(imgs_hwc[i], masks[i], 1, ...) writes. */
+int csm_refine_prepare_many(const uint8_t *const *imgs_hwc, const uint8_t *const *masks, int n, int H, int W, int rh, int rw,
+                            int Hm, int Wm, int rhm, int rwm, int T, float *batch, void *stream);
 
 /* _postprocess_refine tail   animeinsseg/__init__.py:653-662:
  * sigmoid -> crop [:crop_h,:crop_w] -> bilinear(align_corners=True) to (oh,ow) -> > thr ; masks u8 [n,oh,ow]. */

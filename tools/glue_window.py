@@ -10,6 +10,11 @@ no other tracing in that run).  Per step of 8 frames:
                      on a depth queue before the step's first post-processing kernel to the end of its last one; launches and
                      coverage are those of the queues that run post-processing kernels (one per depth stream); host reads: this
                      code path has none (read off the code, not measured)
+  det -> refine    : (f) the detector's post-processing chain on the main queue (the queue that runs k_refine_batch) -- from the end
+                     of the step's last RTMDet program kernel (the last `csmconv::` kernel on that queue before the step's first
+                     k_nms_mask) to the start of its first ISNet program kernel (the first `csmconv::` kernel on that queue after the
+                     step's first k_refine_batch): wall time, launches on that queue and the share of the window that queue covers
+                     (the depth streams keep the GPU busy meanwhile; the detector's host read falls into this window)
 usage: python tools/glue_window.py <kernel_trace.csv> [step_trace output] [frames per step, default 8] [steps to report, default 6]"""
 import csv
 import re
@@ -92,6 +97,42 @@ def main():
         print("  %4d   %11.1f   %13.1f   %12d" % (i, wall / 1e3, 100.0 * cov / max(wall, 1), len(inside)))
         tot[0] += wall; tot[1] += cov; tot[2] += len(inside)
     print("  mean   %11.1f   %13.1f   %12.1f" % (tot[0] / n / 1e3, 100.0 * tot[1] / max(tot[0], 1), tot[2] / n))
+    print("detector post-processing on the main queue (end of the last RTMDet program kernel -> start of the first ISNet program kernel;")
+    print("launches and coverage are those of that queue alone)")
+    print("  step   (a) wall us   (b) covered %   (c) launches")
+    tot = [0.0, 0.0, 0]
+    names, found = {}, 0
+    lo = allfirsts[-nsteps - 1][0] if len(allfirsts) > nsteps else rows[0][0]
+    for i, fb in enumerate(firsts):
+        step = [r for r in rows if lo <= r[0] < fb[0]]
+        lo = fb[0]
+        prep = [r for r in step if "k_refine_batch" in r[2]]
+        nms = [r for r in step if "k_nms_mask" in r[2]]
+        if not prep or not nms:
+            print("  %4d   no k_nms_mask / k_refine_batch launch found" % i)
+            continue
+        q = prep[0][3]
+        main = [r for r in step if r[3] == q]
+        before = [r[1] for r in main if "csmconv::" in r[2] and r[1] <= nms[0][0]]
+        after = [r[0] for r in main if "csmconv::" in r[2] and r[0] >= prep[0][1]]
+        if not before or not after:
+            print("  %4d   no net kernel around the window on queue %s" % (i, q))
+            continue
+        t0, t1 = max(before), min(after)
+        inside = [r for r in main if t0 <= r[0] < t1]
+        cov = union_ns([(s, min(e, t1)) for s, e, _, _ in inside])
+        wall = t1 - t0
+        print("  %4d   %11.1f   %13.1f   %12d" % (i, wall / 1e3, 100.0 * cov / max(wall, 1), len(inside)))
+        tot[0] += wall; tot[1] += cov; tot[2] += len(inside); found += 1
+        for r in inside:
+            k = re.sub(r"[<(].*", "", r[2].replace("void ", "").replace("(anonymous namespace)::", ""))[:60]
+            v = names.setdefault(k, [0, 0])
+            v[0] += 1; v[1] += r[1] - r[0]
+    if found:
+        print("  mean   %11.1f   %13.1f   %12.1f" % (tot[0] / found / 1e3, 100.0 * tot[1] / max(tot[0], 1), tot[2] / found))
+        print("  launches in the window, per step (kernel time us):")
+        for k, v in sorted(names.items(), key=lambda kv: -kv[1][1]):
+            print("    %6.1f x  %8.1f us  %s" % (v[0] / found, v[1] / found / 1e3, k))
 
 
 if __name__ == "__main__":
