@@ -12,7 +12,7 @@ from cartoonsegmentation_amd.nets import build_isnet
 from cartoonsegmentation_amd.runtime import CompiledProgram
 from cartoonsegmentation_amd.segmentation import ANIMESEG_CKPT, animeseg_size, load_animeseg_weights
 
-__all__ = ['AnimeSegmentation', 'load_refinenet', 'get_mask']
+__all__ = ['AnimeSegmentation', 'load_refinenet', 'get_mask', 'get_cutout']
 
 
 class AnimeSegmentation:
@@ -73,14 +73,13 @@ def load_refinenet(refine_method='animeseg', device: str = None) -> AnimeSegment
     return AnimeSegmentation(ws, device or 'cuda').eval()
 
 
-def get_mask(model, input_img, use_amp=True, s=640):
-    """animeseg_refine/__init__.py:169-188: RGB u8 image [h0,w0,3] (numpy or tensor) -> foreground probability float32 numpy
-    [h0,w0,1].  use_amp is ignored (fp32)."""
+def _probability(model, input_img, s, what):
+    """get_mask's chain on the device: (the uint8 image [h0,w0,3], the foreground probability float32 [h0,w0]) as device tensors"""
     L = _lib.load()
     img = input_img if isinstance(input_img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(input_img))
     img = img.to(model.device).contiguous()
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
-        raise _lib.CsmError("get_mask expects a uint8 HxWx3 image")
+        raise _lib.CsmError("%s expects a uint8 HxWx3 image" % what)
     h0, w0 = int(img.shape[0]), int(img.shape[1])
     h, w = animeseg_size(h0, w0, s)
     x = torch.empty((1, 3, s, s), dtype=torch.float32, device=model.device)
@@ -89,4 +88,22 @@ def get_mask(model, input_img, use_amp=True, s=640):
     prob = torch.empty((h0, w0), dtype=torch.float32, device=model.device)
     check(L.csm_animeseg_mask(ptr(logits), i32(s), i32(h), i32(w), i32(h0), i32(w0), f32(0.5), ptr(prob), ptr(None), stream_ptr()),
           "animeseg_mask")
-    return prob.cpu().numpy()[:, :, np.newaxis]
+    return img, prob
+
+
+def get_mask(model, input_img, use_amp=True, s=640):
+    """animeseg_refine/__init__.py:169-188: RGB u8 image [h0,w0,3] (numpy or tensor) -> foreground probability float32 numpy
+    [h0,w0,1].  use_amp is ignored (fp32)."""
+    return _probability(model, input_img, s, "get_mask")[1].cpu().numpy()[:, :, np.newaxis]
+
+
+def get_cutout(model, input_img, use_amp=True, s=640):
+    """anime-seg's "matted" output (the reference's commented-out `rst.png`, animeinsseg/__init__.py:115-116:
+    concatenate((img, mask * 255), axis=2)): get_mask's chain with the probability kept on the device, then the image with the
+    probability as its alpha.  Returns uint8 numpy [h0,w0,4]: the input's three channels in their order, then
+    A = (uint8)(clamp(p, 0, 1) * 255), truncated as the reference's astype does; colour is zero wherever A is 0
+    (ops.cutout_bgra with a float alpha plane).  use_amp is ignored (fp32)."""
+    from cartoonsegmentation_amd import ops
+    img, prob = _probability(model, input_img, s, "get_cutout")
+    whole = torch.ones((1,) + tuple(prob.shape), dtype=torch.uint8, device=prob.device)
+    return ops.cutout_bgra(img, whole, alpha=prob)[0].cpu().numpy()

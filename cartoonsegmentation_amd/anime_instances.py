@@ -185,3 +185,35 @@ class AnimeInstances:
                 canvas[y:y2 + 1, [x, x2]] = col
                 canvas[[y, y2], x:x2 + 1] = col
         return canvas.clip(0, 255).astype(np.uint8)
+
+    # ---- cut-outs with transparency ---------------------------------------------
+    def cutouts(self, img, pad=0, draw_indices=None):
+        """every instance (or those of draw_indices) cut out of the BGR frame `img` (numpy, uploaded, or a device tensor) with
+        transparency: a list of device uint8 [h,w,4] images B, G, R, A over the mask's tight box grown by `pad` and clipped to the
+        frame (ops.cutout_bgra: A = 255 inside the mask, colour and A zero outside); None at the place of an empty mask.  Host
+        instances are uploaded; nothing but the [n,4] box table is read back."""
+        if self.is_empty:
+            return []
+        from . import ops
+        masks = self.masks if self.is_tensor else torch.from_numpy(np.ascontiguousarray(self.masks))
+        masks = masks if masks.is_cuda else masks.cuda()
+        if masks.dtype not in (torch.bool, torch.uint8):
+            masks = masks != 0
+        frame = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+        return ops.cutout_bgra(frame.to(masks.device), masks, pad=pad, indices=draw_indices)
+
+    def save_cutouts(self, img, save_dir, img_name, pad=0):
+        """writes `cutout_{ii:03d}_{img_name}.webp` into save_dir for every instance with a non-empty mask: lossless WebP with
+        alpha, composed and coded on the device (ops.cutout_bgra, ops.webp_encode_lossless, one call each for all instances).
+        Returns the paths."""
+        import os
+        from . import ops
+        cuts = self.cutouts(img, pad=pad)
+        kept = [ii for ii, c in enumerate(cuts) if c is not None]
+        os.makedirs(save_dir, exist_ok=True)
+        paths = []
+        for ii, data in zip(kept, ops.webp_encode_lossless([cuts[ii] for ii in kept])):
+            paths.append(os.path.join(save_dir, 'cutout_' + str(ii).zfill(3) + '_' + img_name + '.webp'))
+            with open(paths[-1], 'wb') as f:
+                f.write(data)
+        return paths

@@ -1087,6 +1087,186 @@ def webp_encode(frames, quality=90):
     return [webpcode.still_file(s) for s in webp_streams(frames, quality=quality)[0]]
 
 
+# ---- lossless WebP of device images (csrc/webpll.hip + webpcode.py; the instance cut-outs, utils.io_utils.imwrite) ------------
+WEBPLL_SCRATCH_BYTES = 256 << 20       # images are coded in chunks whose scratch stays below this (one image is always taken)
+
+
+def _webpll_images(images):
+    """the acceptance rule of webp_encode_lossless: a list of (contiguous uint8 tensor [H,W,C] or [H,W], H, W, C, mask)"""
+    what = "webp_encode_lossless"
+    if isinstance(images, torch.Tensor):
+        if not images.is_cuda:
+            raise _lib.CsmError("%s: images must be device tensors; libcsm355 has no CPU path" % what)
+        if images.dtype == torch.bool:
+            ok, batch = images.dim() in (2, 3), images.dim() == 3
+        else:
+            ok = images.dtype == torch.uint8 and (images.dim() in (2, 3) or (images.dim() == 4 and images.shape[-1] in (3, 4)))
+            batch = images.dim() == 4 or (images.dim() == 3 and images.shape[-1] not in (3, 4))
+        if not ok:
+            raise _lib.CsmError("%s: uint8 [n,H,W,4], [n,H,W,3], [n,H,W], one such image, bool [n,H,W] or [H,W], or a list of "
+                                "images expected (got %s %s)" % (what, images.dtype, tuple(images.shape)))
+        items = list(images.unbind(0)) if batch else [images]
+    elif isinstance(images, (list, tuple)):
+        items = list(images)
+    else:
+        raise _lib.CsmError("%s: a device tensor or a list of device tensors expected (got %s)" % (what, type(images).__name__))
+    out = []
+    for im in items:
+        if not isinstance(im, torch.Tensor) or not im.is_cuda:
+            raise _lib.CsmError("%s: images must be device tensors; libcsm355 has no CPU path" % what)
+        mask = im.dtype == torch.bool
+        if not ((mask and im.dim() == 2) or (im.dtype == torch.uint8 and (im.dim() == 2 or (im.dim() == 3 and im.shape[-1] in (3, 4))))):
+            raise _lib.CsmError("%s: every image must be uint8 [H,W], [H,W,3], [H,W,4] or bool [H,W] (got %s %s)"
+                                % (what, im.dtype, tuple(im.shape)))
+        H, W = int(im.shape[0]), int(im.shape[1])
+        if not (1 <= H <= 16384 and 1 <= W <= 16384):
+            raise ValueError("%s: H and W must be in [1, 16384] (got %dx%d)" % (what, H, W))
+        im = im.contiguous()
+        out.append((im.view(torch.uint8) if mask else im, H, W, int(im.shape[2]) if im.dim() == 3 else 1, mask))
+    if out and any(t[0].device != out[0][0].device for t in out):
+        raise _lib.CsmError("%s: the images must lie on one device" % what)
+    return out
+
+
+def webp_encode_lossless(images):
+    """Lossless WebP files (VP8L; contract DESIGN.md §4.13) of device images: uint8 [n,H,W,4] (B, G, R, A in memory; the file
+    carries the alpha), [n,H,W,3] (B, G, R), [n,H,W] (grey), bool [n,H,W] masks (written 0 / 255), one such image without the
+    leading n (a uint8 tensor of rank 3 whose last dimension is 3 or 4 is one colour image), or a LIST of [H,W] / [H,W,C] tensors
+    of mixed sizes and channel counts.  Returns a list of `bytes`, each a complete .webp file that decodes to the input bit for
+    bit; an empty batch or list gives [].  Subtract-green, the predictor choice, the run parse, the histograms and the bit packing
+    run on the device (csm_webpll_measure / _write), a whole list in one call through a per-image descriptor table, in chunks of
+    images whose scratch stays below WEBPLL_SCRATCH_BYTES; per chunk the host reads the [2k,1088] histogram table once, builds
+    the prefix codes and every header bit (webpcode.ll_image_code), then reads only the compressed bytes."""
+    import ctypes
+    from . import webpcode
+    items = _webpll_images(images)
+    if not items:
+        return []
+    L, dev = _lib.load(), items[0][0].device
+    st = stream_ptr(dev)
+    words, mwords, twords = L.csm_webpll_desc_words(), L.csm_webpll_measure_words(), L.csm_webpll_table_words()
+    assert (words, mwords, twords) == (8, webpcode.LL_SYMS, webpcode.LL_TABLE_WORDS)
+    c_desc = ctypes.POINTER(ctypes.c_int64)
+
+    def descriptors(part):
+        desc = _np.zeros((len(part), words), _np.int64)
+        for j, (im, H, W, C, mask) in enumerate(part):
+            desc[j, :4] = (im.data_ptr(), H, W, C | (256 if mask else 0))
+        need = L.csm_webpll_plan(desc.ctypes.data_as(c_desc), i32(len(part)))
+        if not need:
+            raise _lib.CsmError("webp_encode_lossless: the library refused the descriptors of %d images" % len(part))
+        return desc, need
+
+    own = [descriptors([it])[1] for it in items]
+    out, i = [], 0
+    while i < len(items):
+        k, total = 1, own[i]
+        while i + k < len(items) and total + own[i + k] <= WEBPLL_SCRATCH_BYTES:
+            total += own[i + k]
+            k += 1
+        part = items[i:i + k]
+        i += k
+        desc, need = descriptors(part)
+        desc_h = desc.ctypes.data_as(c_desc)
+        desc_d = torch.from_numpy(desc).to(dev)
+        table = torch.empty((2 * k, mwords), dtype=torch.int32, device=dev)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(L.csm_webpll_measure(desc_h, ptr(desc_d), i32(k), ptr(table), ptr(scratch), st), "webpll_measure")
+        table_h = table.cpu().numpy().view(_np.uint32)      # the one sync: the histograms size every stream exactly
+        rows, spans, total = _np.empty((2 * k, twords), _np.uint32), [], 0
+        for j, (im, H, W, C, mask) in enumerate(part):
+            code = webpcode.ll_image_code(table_h[2 * j], table_h[2 * j + 1], W, H, C == 4)
+            rows[2 * j] = webpcode.ll_table_row(code['planes'][0], total, code['bytes'])
+            rows[2 * j + 1] = webpcode.ll_table_row(code['planes'][1], total, code['bytes'])
+            spans.append((total, code['bytes']))
+            total += (code['bytes'] + 3) & ~3
+        host_table = torch.from_numpy(rows.view(_np.int32)).to(dev)
+        blob = torch.empty(total, dtype=torch.uint8, device=dev)
+        check(L.csm_webpll_write(desc_h, ptr(desc_d), i32(k), ptr(host_table), ptr(blob), i64(total), ptr(scratch), st), "webpll_write")
+        host = blob.cpu().numpy().tobytes()
+        out += [webpcode.lossless_file(host[o:o + b]) for o, b in spans]
+    return out
+
+
+# ---- instance cut-outs with transparency (csrc/cutout.hip) --------------------------------------------------------------------
+def _cutout_masks(masks, what):
+    if not (isinstance(masks, torch.Tensor) and masks.is_cuda):
+        raise _lib.CsmError("%s: masks must be a device tensor; libcsm355 has no CPU path" % what)
+    if masks.dtype not in (torch.uint8, torch.bool) or masks.dim() != 3:
+        raise _lib.CsmError("%s: uint8 or bool masks [n,H,W] expected (got %s %s)" % (what, masks.dtype, tuple(masks.shape)))
+    m = masks.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def mask_bboxes(masks):
+    """The tight boxes of device masks uint8 / bool [n,H,W]: a device int32 [n,4] = x0, y0, x1, y1, end-exclusive; an empty mask
+    gives 0, 0, 0, 0 (csm_mask_bbox: one launch for any n)."""
+    m = _cutout_masks(masks, "mask_bboxes")
+    n, H, W = (int(v) for v in m.shape)
+    boxes = torch.empty((n, 4), dtype=torch.int32, device=m.device)
+    if n and (H < 1 or W < 1):
+        raise _lib.CsmError("mask_bboxes: empty mask planes (got %s)" % (tuple(m.shape),))
+    if n:
+        check(_lib.load().csm_mask_bbox(ptr(m), i32(n), i32(H), i32(W), ptr(boxes), stream_ptr(m.device)), "mask_bbox")
+    return boxes
+
+
+def cutout_bgra(img, masks, alpha=None, pad=0, indices=None):
+    """Instance cut-outs with transparency: for every mask (or those of `indices`) the frame's pixels inside the mask's tight box,
+    grown by `pad` >= 0 and clipped to the frame, as a device uint8 [h,w,4] image B, G, R, A.  A is 255 where the mask is set, or
+    with a float32 alpha plane [H,W] (uint8)(clamp(alpha, 0, 1) * 255), truncated, where the mask is set; 0 elsewhere, and colour
+    is zero wherever A is 0.  img: device uint8 [H,W,3] (B, G, R); masks: device uint8 / bool [n,Hm,Wm], the frame's size or up to
+    2 px smaller (the overlap is used).  Returns a list of views of ONE packed buffer, None at the place of an empty mask.  The
+    only readback is the [n,4] box table, which sizes the buffer; every instance is composed in one launch (csm_cutout_bgra)."""
+    import ctypes
+    what = "cutout_bgra"
+    if not (isinstance(img, torch.Tensor) and img.is_cuda):
+        raise _lib.CsmError("%s: img must be a device tensor; libcsm355 has no CPU path" % what)
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[-1] != 3:
+        raise _lib.CsmError("%s: a uint8 frame [H,W,3] expected (got %s %s)" % (what, img.dtype, tuple(img.shape)))
+    m = _cutout_masks(masks, what)
+    H, W = int(img.shape[0]), int(img.shape[1])
+    n, Hm, Wm = (int(v) for v in m.shape)
+    if not (0 <= H - Hm <= 2 and 0 <= W - Wm <= 2) or Hm < 1 or Wm < 1:
+        raise _lib.CsmError("%s: masks of %dx%d do not fit a frame of %dx%d (the same size or up to 2 px smaller)" % (what, Hm, Wm, H, W))
+    if isinstance(pad, bool) or int(pad) != pad or pad < 0:
+        raise ValueError("%s: pad must be an integer >= 0 (got %r)" % (what, pad))
+    pad = int(pad)
+    if alpha is not None:
+        if not (isinstance(alpha, torch.Tensor) and alpha.is_cuda and alpha.dtype == torch.float32 and tuple(alpha.shape) == (H, W)):
+            raise _lib.CsmError("%s: alpha must be a device float32 plane [%d,%d]" % (what, H, W))
+        alpha = alpha.contiguous()
+    idx = list(range(n)) if indices is None else [int(v) for v in indices]
+    if any(not 0 <= v < n for v in idx):
+        raise IndexError("%s: indices must lie in [0, %d)" % (what, n))
+    if not idx:
+        return []
+    im = img.contiguous()
+    L, dev, st = _lib.load(), im.device, stream_ptr(im.device)
+    boxes = mask_bboxes(m).cpu().numpy()                    # the one readback: it sizes the buffer
+    words = L.csm_cutout_job_words()
+    jobs, shapes, total, pixels = [], [], 0, 0
+    for v in idx:
+        x0, y0, x1, y1 = (int(b) for b in boxes[v])
+        if x1 <= x0 or y1 <= y0:
+            shapes.append(None)
+            continue
+        x0, y0, x1, y1 = max(0, x0 - pad), max(0, y0 - pad), min(W, x1 + pad), min(H, y1 + pad)
+        jobs.append((v, x0, y0, x1, y1, total, pixels, 0))
+        shapes.append((total, y1 - y0, x1 - x0))
+        pixels += (y1 - y0) * (x1 - x0)
+        total = pixels * 4
+    if not jobs:
+        return [None] * len(idx)
+    jobs_h = _np.array(jobs, _np.int64).reshape(-1, words)
+    jobs_d = torch.from_numpy(jobs_h).to(dev)
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    check(L.csm_cutout_bgra(ptr(im), i32(H), i32(W), ptr(m), i32(n), i32(Hm), i32(Wm), ptr(alpha),
+                            jobs_h.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ptr(jobs_d), i32(len(jobs)), ptr(out), i64(total), st),
+          "cutout_bgra")
+    return [None if s is None else out[s[0]:s[0] + s[1] * s[2] * 4].view(s[1], s[2], 4) for s in shapes]
+
+
 # ---- GIF of device frames (csrc/gif.hip + gifcode.py; video.write_gif, npyframes2video's .gif route) ----------------------
 GIF_SCRATCH_BYTES = 64 << 20           # frames are coded in chunks whose scratch stays below this (one frame is always taken)
 

@@ -301,14 +301,19 @@ class AnimeInsSeg:
 
     # ---- COCO annotation export (reference :506-621, :667-693) -------------------------------------------
     def _infer_save_annotations(self, imgs, pred_score_thr, save_dir, save_annotation, obj_id_start, img_id_start, val_dir,
-                                save_mask_only: bool = False):
+                                save_mask_only: bool = False, save_cutout_only: bool = False):
         """infer every image and write the COCO instance-segmentation file `save_annotation`; returns None.  Frames run in chunks of
         det_batch (the batched detector / refine when a chunk's frames are equally sized); each chunk's masks are RLE-encoded on the
         device (ops.mask_rle_encode) and released before the next chunk, and no mask is copied to the host.
 
         save_mask_only (reference :597-598, :616): instead of the file, one 0 / 255 grey `mask_{ii:03d}_{img_name}.png` per instance
         in save_dir, PNG-encoded on the device (ops.png_encode); no JSON is written.  infer() does not forward it, as in the
-        reference."""
+        reference.
+
+        save_cutout_only (the reference's commented-out `rst.png`, :115-116): instead of the file, one
+        `cutout_{ii:03d}_{img_name}.webp` per instance in save_dir: the instance cut out of its frame with transparency, composed
+        and coded as lossless WebP on the device from each chunk's device masks (AnimeInstances.save_cutouts); no
+        JSON is written, and infer() does not forward it."""
         from utils.constants import CATEGORIES
         from utils.io_utils import dict2json, find_all_imgs
         from . import ops
@@ -340,7 +345,10 @@ class AnimeInsSeg:
                     image_id = imgp2ids[src]
                 im_h, im_w = (int(v) for v in frame.shape[:2])
                 image_meta.append({"id": image_id, "height": im_h, "width": im_w, "file_name": img_name})
-                if save_mask_only:
+                if save_cutout_only:
+                    if not inst.is_empty:
+                        inst.save_cutouts(frame, save_dir, img_name)
+                elif save_mask_only:
                     if not inst.is_empty:
                         for j, data in enumerate(ops.png_encode(inst.masks.bool())):
                             with open(os.path.join(save_dir, 'mask_' + str(j).zfill(3) + '_' + img_name + '.png'), 'wb') as f:
@@ -358,7 +366,7 @@ class AnimeInsSeg:
                         obj_id += 1
                 image_id += 1
             del insts, frames
-        if not save_mask_only:
+        if not (save_mask_only or save_cutout_only):
             dict2json({"info": {}, "licenses": [], "images": image_meta, "annotations": det_annotations, "categories": CATEGORIES},
                       save_annotation)
         return None

@@ -696,6 +696,51 @@ int csm_webp_stage(int stage, const uint8_t *frames, int n, int H, int W, int qu
 int csm_webp_measure(const uint8_t *frames, int n, int H, int W, int quality, int64_t *info, void *scratch, void *stream);
 int csm_webp_write(int n, int H, int W, uint8_t *out, int64_t out_bytes, void *scratch, void *stream);
 
+/* The VP8L payload of a lossless WebP file for n images of any sizes (webpll.hip; contract DESIGN.md §4.13, restated in
+ * tests/webpll_restatement.py, byte-identical).  One descriptor per image, int64 [n][csm_webpll_desc_words() = 8]: [0] the device
+ * address of its contiguous u8 pixels [H][W][channels], [1] H, [2] W (1..16384), [3] channels | flags << 8: 1 (grey), 3 (B, G, R) or
+ * 4 (B, G, R, A; the header's alpha bit is set exactly then), flag bit 0 = grey bytes are a mask (any non-zero byte is written as
+ * 255), [4..6] filled by csm_webpll_plan: the image's first residual pixel, first 16 x 16 block and first row unit in scratch
+ * (a row unit is a row of the mode image or of the residual image), [7] 0.  The blocks and the row units of a call each stay
+ * below 2^31 - 1.
+ * csm_webpll_plan: checks desc_host, fills its words [4..7] and returns the device bytes of scratch the two calls share (0 for
+ *   invalid descriptors or n < 1): 4 B per pixel, 4 B per block, 12 B per row unit.
+ * csm_webpll_measure: desc_host and desc_dev (a device copy) as planned.  Subtract-green, the predictor mode of every block (the
+ *   mode 0..12 with the smallest sum of min(r, 256 - r), ties to the lowest), the residuals, and table device uint32
+ *   [2n][csm_webpll_measure_words() = 1088]: for the mode image (row 2i) and the residual image (row 2i + 1) of image i the counts
+ *   of green and the 24 length prefixes [0..279], red [280..535], blue [536..791], alpha [792..1047], the 40 distance prefixes
+ *   [1048..1087] of the row-wise run parse (four literals, then distance-1 references of up to 4096 pixels).
+ * csm_webpll_write: host_table device uint32 [2n][csm_webpll_table_words() = 1352], filled by the host from the measured table:
+ *   [0..1087] bit-reversed code | code length << 16 of every symbol (length 0: the one symbol of a simple code, no bits),
+ *   [1088..1089] byte offset of the image's payload in out (low, high word; a multiple of 4), [1090] bytes of the payload,
+ *   [1091..1092] the bit of the payload at which the plane's pixels begin, [1093] [1094] first 32-bit word and number of words of
+ *   the header bits in front of them, [1095..1350] those words, shifted onto the payload's words.  out: out_bytes device bytes (a
+ *   multiple of 4, 4-aligned), zeroed by the call.  Nothing is written at or past a payload's bytes rounded up to 4, nor past
+ *   out_bytes.  Same descriptors and scratch as the measure call.
+ * Async on the stream, no allocation, no sync; the only atomics are integer adds (counts) and integer ORs of disjoint bits, so
+ * the output is deterministic. */
+int csm_webpll_desc_words(void);
+int csm_webpll_measure_words(void);
+int csm_webpll_table_words(void);
+size_t csm_webpll_plan(int64_t *desc_host, int n);
+int csm_webpll_measure(const int64_t *desc_host, const int64_t *desc_dev, int n, uint32_t *table, void *scratch, void *stream);
+int csm_webpll_write(const int64_t *desc_host, const int64_t *desc_dev, int n, const uint32_t *host_table, uint8_t *out,
+                     int64_t out_bytes, void *scratch, void *stream);
+
+/* Instance cut-outs with transparency (cutout.hip).
+ * csm_mask_bbox: masks u8 / bool [n][H][W] (non-zero = set), H * W < 2^31 -> boxes int32 [n][4] = the tight x0, y0, x1, y1,
+ *   end-exclusive; 0, 0, 0, 0 for an empty mask.  One workgroup per mask and band of 32 rows, integer min / max atomics.
+ * csm_cutout_bgra: img u8 [H][W][3] (B, G, R); masks u8 / bool [n_masks][Hm][Wm] with Hm <= H <= Hm + 2 and Wm <= W <= Wm + 2 (the
+ *   overlap is used: a pixel outside the mask is not set); alpha NULL or fp32 [H][W].  jobs: int64 [k][csm_cutout_job_words() = 8],
+ *   on the host (checked) and a device copy (read by the kernel): [0] mask index, [1..4] the box x0, y0, x1, y1 inside the frame,
+ *   not empty, [5] byte offset of the instance's [y1 - y0][x1 - x0][4] pixels B, G, R, A in out (a multiple of 4), [6] the pixels
+ *   of the jobs before it, [7] 0.  A = 255 where the mask is set, or (uint8)(min(max(alpha, 0), 1) * 255.0f) (truncated) there
+ *   with an alpha plane, 0 elsewhere; B = G = R = 0 wherever A = 0.  One launch over the pixels of all jobs. */
+int csm_mask_bbox(const uint8_t *masks, int n, int H, int W, int32_t *boxes, void *stream);
+int csm_cutout_job_words(void);
+int csm_cutout_bgra(const uint8_t *img, int H, int W, const uint8_t *masks, int n_masks, int Hm, int Wm, const float *alpha,
+                    const int64_t *jobs_host, const int64_t *jobs_dev, int k, uint8_t *out, int64_t out_bytes, void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */

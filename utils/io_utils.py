@@ -99,19 +99,21 @@ def imread_device(path, device=None, progressive=None):
 def imwrite(img, file_path, auto_mkdir=True):
     """mmcv.imwrite / cv2.imwrite stand-in: `img` is a BGR [H,W,3] or grey [H,W] uint8 image, a numpy array (uploaded) or a device
     tensor; it is compressed on the MI355X and only the file's bytes reach the host.  .png: lossless (ops.png_encode); .jpg /
-    .jpeg: ops.jpeg_encode at cv2's defaults (quality 95, 4:2:0; colour only).  Any other suffix raises ValueError.  Returns
-    True."""
+    .jpeg: ops.jpeg_encode at cv2's defaults (quality 95, 4:2:0; colour only); .webp: lossless WebP (ops.webp_encode_lossless),
+    which alone also takes a B, G, R, A image [H,W,4] and writes its alpha.  Any other suffix raises ValueError.  Returns True."""
     suffix = Path(str(file_path)).suffix.lower()
-    if suffix not in ('.png', '.jpg', '.jpeg'):
-        raise ValueError("imwrite: %r is not written here (.png, .jpg and .jpeg are)" % suffix)
+    if suffix not in ('.png', '.jpg', '.jpeg', '.webp'):
+        raise ValueError("imwrite: %r is not written here (.png, .jpg, .jpeg and .webp are)" % suffix)
     import torch
     from cartoonsegmentation_amd import ops
     t = img if isinstance(img, torch.Tensor) else torch.tensor(np.asarray(img)).cuda()
     if t.dim() == 3 and t.shape[2] == 1:
         t = t[:, :, 0]
-    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 3):
-        raise ValueError("imwrite: an [H,W] or [H,W,3] image is expected (got shape %s)" % (tuple(t.shape),))
-    if suffix == '.png':
+    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 3 and not (suffix == '.webp' and t.shape[2] == 4)):
+        raise ValueError("imwrite: an [H,W] or [H,W,3] image (for .webp also [H,W,4]) is expected (got shape %s)" % (tuple(t.shape),))
+    if suffix == '.webp':
+        data = ops.webp_encode_lossless([t])[0]
+    elif suffix == '.png':
         data = ops.png_encode(t.unsqueeze(0), bgr=True)[0]
     else:
         if t.dim() == 2:
