@@ -167,8 +167,17 @@ class AnimeInstances:
             self.to_numpy()
 
     def draw_instances(self, img, draw_bbox=True, draw_ins_mask=True, draw_ins_contour=False, draw_tags=False,
-                       draw_indices=None, mask_alpha=0.4):
-        """overlay masks (alpha blend) and box outlines on a BGR image; returns uint8 HxWx3"""
+                       draw_indices=None, mask_alpha=0.4, on_device=False):
+        """overlay masks (alpha blend) and box outlines on a BGR image; returns uint8 HxWx3.
+
+        on_device=True draws the reference's picture on the device instead (ops.draw_instances) and returns a
+        device uint8 [H,W,3] tensor: alpha 0.75 whatever mask_alpha says (reference :140), all boxes first at the reference's line
+        width, then the masks; host instances and a numpy frame are uploaded.  draw_tags draws nothing: tags are empty here
+        (infer_tags is not built) and the reference skips empty tags.  The box edge is a crisp band, not cv2's LINE_AA [EXT]."""
+        if on_device:
+            from . import ops
+            return ops.draw_instances_many([img], [self], indices=None if draw_indices is None else [draw_indices], draw_bbox=draw_bbox,
+                                           draw_ins_mask=draw_ins_mask, draw_ins_contour=draw_ins_contour, mask_alpha=0.75)[0]
         canvas = np.array(img, dtype=np.float32, copy=True)
         if self.is_empty:
             return canvas.astype(np.uint8)
@@ -185,6 +194,12 @@ class AnimeInstances:
                 canvas[y:y2 + 1, [x, x2]] = col
                 canvas[[y, y2], x:x2 + 1] = col
         return canvas.clip(0, 255).astype(np.uint8)
+
+    def save_visualization(self, img, out_file):
+        """the picture of draw_instances(img, on_device=True) written to out_file through utils.io_utils.imwrite: .png, .jpg / .jpeg
+        and .webp are coded on the device, any other suffix is imwrite's ValueError"""
+        from utils.io_utils import imwrite
+        return imwrite(self.draw_instances(img, on_device=True), out_file)
 
     # ---- cut-outs with transparency (DESIGN.md §4.13) ---------------------------------------------
     def cutouts(self, img, pad=0, draw_indices=None):

@@ -1267,6 +1267,114 @@ def cutout_bgra(img, masks, alpha=None, pad=0, indices=None):
     return [None if s is None else out[s[0]:s[0] + s[1] * s[2] * 4].view(s[1], s[2], 4) for s in shapes]
 
 
+# ---- instance overlays (csrc/overlay.hip) ------------------------------------------------------------------------
+def overlay_line_width(H, W):
+    """the reference's box line width (anime_instances.py:166): max(round((H + W + 3) / 2 * 0.003), 2), Python's round"""
+    return max(round((H + W + 3) / 2 * 0.003), 2)
+
+
+def _per_frame(value, n, name):
+    if value is None:
+        return [None] * n
+    if not isinstance(value, (list, tuple)) or len(value) != n:
+        raise ValueError("draw_instances_many: %s must be None or a list with one entry per frame" % name)
+    return list(value)
+
+
+def draw_instances_many(frames, instances, colors=None, indices=None, draw_bbox=True, draw_ins_mask=True, draw_ins_contour=False,
+                        mask_alpha=0.75, line_width=None):
+    """ops.draw_instances for a list of frames, which may differ in size, in ONE native call (csm_draw_instances).  instances: per
+    frame an object with .masks and .bboxes (AnimeInstances; masks None = no instance) or a (masks, bboxes) pair; colors and
+    indices: None or a list with one entry (or None) per frame.  Returns a list of device uint8 [H,W,3] tensors."""
+    import ctypes
+    from .anime_instances import get_color
+    what = "draw_instances"
+    frames, instances = list(frames), list(instances)
+    if len(frames) != len(instances):
+        raise ValueError("%s: %d frames but %d sets of instances" % (what, len(frames), len(instances)))
+    colors, indices = _per_frame(colors, len(frames), "colors"), _per_frame(indices, len(frames), "indices")
+    if isinstance(mask_alpha, bool) or not 0.0 <= float(mask_alpha) <= 1.0:
+        raise ValueError("%s: mask_alpha must lie in [0, 1] (got %r)" % (what, mask_alpha))
+    if line_width is not None and (isinstance(line_width, bool) or int(line_width) != line_width or not 1 <= line_width < 1 << 30):
+        raise ValueError("%s: line_width must be an integer >= 1 (got %r)" % (what, line_width))
+    if not frames:
+        return []
+    L = _lib.load()
+    words = L.csm_overlay_job_words()
+    jobs_h = _np.zeros((len(frames), words), _np.int64)
+    entries, cols, keep, outs = [], [], [], []
+    for j, (frame, inst) in enumerate(zip(frames, instances)):
+        im = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(_np.ascontiguousarray(frame))
+        im = (im if im.is_cuda else im.cuda()).contiguous()
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[-1] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise _lib.CsmError("%s: a uint8 frame [H,W,3] expected (got %s %s)" % (what, im.dtype, tuple(im.shape)))
+        H, W = int(im.shape[0]), int(im.shape[1])
+        masks, boxes = (inst.masks, inst.bboxes) if hasattr(inst, 'masks') else inst
+        n = 0 if masks is None else len(masks)
+        m = b = None
+        if n:
+            m = masks if isinstance(masks, torch.Tensor) else torch.from_numpy(_np.ascontiguousarray(masks))
+            if m.dtype not in (torch.uint8, torch.bool) or m.dim() != 3:
+                raise _lib.CsmError("%s: uint8 or bool masks [n,H,W] expected (got %s %s)" % (what, m.dtype, tuple(m.shape)))
+            if tuple(m.shape[1:]) != (H, W):
+                raise ValueError("%s: masks of %dx%d over a frame of %dx%d: the reference's cv2.resize(INTER_AREA) of the frame to the "
+                                 "masks' size (anime_instances.py:151-153) is not built; resize the instances to the frame"
+                                 % (what, m.shape[1], m.shape[2], H, W))
+            m = m.to(im.device).contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m
+            b = boxes if isinstance(boxes, torch.Tensor) else torch.from_numpy(_np.ascontiguousarray(boxes))
+            if tuple(b.shape) != (n, 4) or b.dtype.is_floating_point or b.dtype == torch.bool:
+                raise _lib.CsmError("%s: integer xywh boxes [%d,4] expected (got %s %s)" % (what, n, b.dtype, tuple(b.shape)))
+            b = b.to(im.device, torch.int32).contiguous()
+        idx = list(range(n)) if indices[j] is None else [int(v) for v in indices[j]]
+        if any(not 0 <= v < n for v in idx):
+            raise ValueError("%s: draw indices must lie in [0, %d) (got %r)" % (what, n, idx))
+        if colors[j] is None:
+            col = _np.array([get_color(v) for v in idx], _np.uint8).reshape(-1, 3)
+        else:
+            col = colors[j].cpu().numpy() if isinstance(colors[j], torch.Tensor) else _np.asarray(colors[j])
+            if col.shape != (len(idx), 3) or col.dtype != _np.uint8:
+                raise ValueError("%s: colors must be uint8 [%d,3], one B, G, R per draw-list entry (got %s %s)"
+                                 % (what, len(idx), col.dtype, col.shape))
+        out = torch.empty_like(im)
+        jobs_h[j, :10] = (im.data_ptr(), out.data_ptr(), 0 if m is None else m.data_ptr(), 0 if b is None else b.data_ptr(), H, W, n,
+                          len(idx), len(entries), overlay_line_width(H, W) if line_width is None else int(line_width))
+        entries += idx
+        cols.append(col)
+        keep.append((im, m, b))
+        outs.append(out)
+    dev = keep[0][0].device
+    if any(k[0].device != dev for k in keep):
+        raise _lib.CsmError("%s: the frames of one call must be on one device" % what)
+    i64p, i32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    if not L.csm_overlay_plan(jobs_h.ctypes.data_as(i64p), i32(len(frames)), i32(len(entries))):
+        raise _lib.CsmError("%s: csm_overlay_plan refused the job table" % what)
+    flags = (1 if draw_bbox else 0) | (2 if draw_ins_mask else 0) | (4 if draw_ins_contour else 0)
+    entries_h = _np.array(entries, _np.int32)
+    alpha = _np.float32(mask_alpha)
+    jobs_d = torch.from_numpy(jobs_h).to(dev)
+    entries_d = torch.from_numpy(entries_h).to(dev) if entries else None
+    cols_d = torch.from_numpy(_np.concatenate(cols)).to(dev) if entries else None
+    check(L.csm_draw_instances(jobs_h.ctypes.data_as(i64p), ptr(jobs_d), i32(len(frames)), entries_h.ctypes.data_as(i32p), ptr(entries_d),
+                               ptr(cols_d), i32(len(entries)), i32(flags), f32(float(alpha)), f32(float(_np.float32(1) - alpha)),
+                               stream_ptr(dev)), what)
+    return outs
+
+
+def draw_instances(img, masks, bboxes, colors=None, indices=None, draw_bbox=True, draw_ins_mask=True, draw_ins_contour=False,
+                   mask_alpha=0.75, line_width=None):
+    """The reference's instance picture (AnimeInstances.draw_instances, anime_instances.py:131-194) drawn on the device, byte-exact
+    to the contract of DESIGN.md §4.14: a device uint8 [H,W,3] copy of the B, G, R frame `img` (numpy, uploaded, or a device tensor)
+    with, for the instances of `indices` (any order, repeats allowed; default all) in that order, first every box outline
+    (`bboxes` int xywh [n,4]; a crisp band `line_width` px thick, default the reference's rule), then every mask (`masks` bool or
+    0 / 1 uint8 [n,H,W]) blended in float32 as d = d * (1 - mask_alpha) + mask_alpha * colour and truncated, then, with
+    draw_ins_contour, every mask's edge pixels in its colour.  colors: uint8 [k,3] B, G, R per draw-list entry (default
+    get_color(instance index)).  Masks of another size than the frame and indices outside 0..n-1 raise ValueError."""
+    return draw_instances_many([img], [(masks, bboxes)], colors=None if colors is None else [colors],
+                               indices=None if indices is None else [indices], draw_bbox=draw_bbox, draw_ins_mask=draw_ins_mask,
+                               draw_ins_contour=draw_ins_contour, mask_alpha=mask_alpha, line_width=line_width)[0]
+
+
 # ---- GIF of device frames (csrc/gif.hip + gifcode.py; video.write_gif, npyframes2video's .gif route) ----------------------
 GIF_SCRATCH_BYTES = 64 << 20           # frames are coded in chunks whose scratch stays below this (one frame is always taken)
 

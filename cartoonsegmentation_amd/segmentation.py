@@ -238,7 +238,8 @@ class AnimeInsSeg:
             self.set_refine_method(**refine_kwargs)
         self.set_max_instance(max_instances)
         if save_visualization or infer_tags:
-            raise NotImplementedError("visualization / tagging are outside the hot-path scope (SURVEY 2.1)")
+            raise NotImplementedError("infer() does not draw or tag (SURVEY 2.1); pictures are written by save_visualization(out_file, img, "
+                                      "instances) and _infer_save_annotations(..., save_visualization_only=True)")
         if isinstance(imgs, str) and imgs.endswith('.txt'):         # reference :437-439: a list of image paths
             from utils.io_utils import read_imglst_from_txt
             imgs = read_imglst_from_txt(imgs)
@@ -301,7 +302,7 @@ class AnimeInsSeg:
 
     # ---- COCO annotation export (reference :506-621, :667-693) -------------------------------------------
     def _infer_save_annotations(self, imgs, pred_score_thr, save_dir, save_annotation, obj_id_start, img_id_start, val_dir,
-                                save_mask_only: bool = False, save_cutout_only: bool = False):
+                                save_mask_only: bool = False, save_cutout_only: bool = False, save_visualization_only: bool = False):
         """infer every image and write the COCO instance-segmentation file `save_annotation`; returns None.  Frames run in chunks of
         det_batch (the batched detector / refine when a chunk's frames are equally sized); each chunk's masks are RLE-encoded on the
         device (ops.mask_rle_encode) and released before the next chunk, and no mask is copied to the host.
@@ -313,7 +314,12 @@ class AnimeInsSeg:
         save_cutout_only (the reference's commented-out `rst.png`, :115-116): instead of the file, one
         `cutout_{ii:03d}_{img_name}.webp` per instance in save_dir: the instance cut out of its frame with transparency, composed
         and coded as lossless WebP on the device from each chunk's device masks (AnimeInstances.save_cutouts); no
-        JSON is written, and infer() does not forward it."""
+        JSON is written, and infer() does not forward it.
+
+        save_visualization_only (the reference's save_visualization branch, :582-584): instead of the file, one picture per image,
+        `save_dir/<img_name>` (the reference's out_file), the instances drawn over the frame and the file coded on the device
+        (ops.draw_instances_many, one call per chunk; utils.io_utils.imwrite); no JSON is written, and infer() does
+        not forward it.  A target that is the same file as its source image is a ValueError before anything is written."""
         from utils.constants import CATEGORIES
         from utils.io_utils import dict2json, find_all_imgs
         from . import ops
@@ -332,6 +338,10 @@ class AnimeInsSeg:
             imgs = [imgs]
         if save_dir == '':
             save_dir = os.path.join(target_dir, os.path.basename(str(self.ckpt)).replace('.ckpt', '').replace('.pth', '').replace('.pt', ''))
+        if save_visualization_only:
+            for src in imgs:
+                if isinstance(src, str) and os.path.realpath(os.path.join(save_dir, os.path.basename(src))) == os.path.realpath(src):
+                    raise ValueError("save_visualization_only: %s would be overwritten by its own picture; choose another save_dir" % src)
         os.makedirs(save_dir, exist_ok=True)
         image_meta, det_annotations = [], []
         obj_id, image_id = obj_id_start + 1, img_id_start + 1
@@ -339,6 +349,11 @@ class AnimeInsSeg:
             chunk = imgs[c0:c0 + self.det_batch]
             frames = self._load(chunk)
             insts = self._infer_frames(frames, pred_score_thr)
+            if save_visualization_only:
+                from utils.io_utils import imwrite
+                for k, (src, drawn) in enumerate(zip(chunk, ops.draw_instances_many(frames, insts))):
+                    imwrite(drawn, os.path.join(save_dir, os.path.basename(src) if isinstance(src, str) else f'{c0 + k}'.zfill(12) + '.jpg'))
+                continue
             for k, (src, frame, inst) in enumerate(zip(chunk, frames, insts)):
                 img_name = os.path.basename(src) if isinstance(src, str) else f'{c0 + k}'.zfill(12) + '.jpg'
                 if imgp2ids is not None:
@@ -366,10 +381,15 @@ class AnimeInsSeg:
                         obj_id += 1
                 image_id += 1
             del insts, frames
-        if not (save_mask_only or save_cutout_only):
+        if not (save_mask_only or save_cutout_only or save_visualization_only):
             dict2json({"info": {}, "licenses": [], "images": image_meta, "annotations": det_annotations, "categories": CATEGORIES},
                       save_annotation)
         return None
+
+    def save_visualization(self, out_file: str, img, instances):
+        """reference :696-698: the instances drawn over `img` (AnimeInstances.draw_instances(on_device=True)) written to out_file;
+        drawn and coded on the device (AnimeInstances.save_visualization)"""
+        return instances.save_visualization(img, out_file)
 
     # ---- detector forward + post-process (reference :447-462 + mmdet predict_by_feat) ---------------
     def _upload(self, img):

@@ -741,6 +741,30 @@ int csm_cutout_job_words(void);
 int csm_cutout_bgra(const uint8_t *img, int H, int W, const uint8_t *masks, int n_masks, int Hm, int Wm, const float *alpha,
                     const int64_t *jobs_host, const int64_t *jobs_dev, int k, uint8_t *out, int64_t out_bytes, void *stream);
 
+/* Instance overlays: box outlines, alpha-blended masks and contours drawn over B, G, R frames (overlay.hip; DESIGN.md §4.14;
+ * restated in tests/overlay_restatement.py, byte-identical).  One call draws a chunk of frames of any sizes.
+ * jobs: int64 [n_jobs][csm_overlay_job_words() = 16], on the host (checked) and a device copy (read by the kernels): [0] [1] the
+ *   device addresses of the frame u8 [H][W][3] and of the picture (same shape, another buffer), [2] of its masks u8 / bool
+ *   [n_masks][H][W] (non-zero = set), [3] of its boxes int32 [n_masks][4] = x, y, w, h (device data, any values), [4] H, [5] W
+ *   (H * W < 2^31 - 1), [6] n_masks, [7] k, the entries of its draw list, [8] its first entry in `entries`, [9] the line width
+ *   t >= 1, [10..12] filled by csm_overlay_plan (its first 128 x 8 tile, tiles per row, tiles), [13..15] 0.  [2] and [3] may be 0 when k = 0.
+ * entries: int32 [n_entries], host (checked: 0 <= entry < the job's n_masks) and device copy, the draw lists of all jobs; colors:
+ *   device u8 [n_entries][3], the B, G, R of every entry.
+ * flags: 1 boxes, 2 masks, 4 contours.  In list order: (1) for every entry the pixels inside
+ *   [x - a, x + w + a] x [y - a, y + h + a] and not inside [x + b, x + w - b] x [y + b, y + h - b] (a = t / 2, b = t - a, bounds
+ *   inclusive) take its colour; (2) in fp32, for every entry whose mask is set at the pixel, d = fl(fl(d * one_minus_alpha) +
+ *   fl(alpha * c)), no fused multiply-add, then d is truncated to u8; (3) every mask pixel with a 4-neighbour outside the mask or
+ *   the frame takes the entry's colour.  A frame with k = 0 is copied.
+ * csm_overlay_plan: checks jobs_host, fills its words [10..15] and returns the tiles of the call (0 for an invalid table).
+ * csm_draw_instances: one launch, a workgroup per tile, every tile walks its frame's whole draw list, so n and the overlap depth
+ *   are unbounded and every mask byte is read once.  Mask rows are read as aligned 4-byte words that hold at least one byte of
+ *   the row.  Async on the stream, no allocation, no scratch, no sync, no readback, no atomics: the output is deterministic. */
+int csm_overlay_job_words(void);
+int csm_overlay_plan(int64_t *jobs_host, int n_jobs, int n_entries);
+int csm_draw_instances(const int64_t *jobs_host, const int64_t *jobs_dev, int n_jobs, const int32_t *entries_host,
+                       const int32_t *entries_dev, const uint8_t *colors_dev, int n_entries, int flags, float alpha,
+                       float one_minus_alpha, void *stream);
+
 /* Detector input: mmdet test pipeline Resize(keep_ratio) + Pad(pad_value) + DetDataPreprocessor normalise
  * (call sites animeinsseg/__init__.py:63-76, :212-215, :395-399).  img u8 HWC [H,W,3] (BGR) -> fp32 NCHW
  * [1,3,S_h,S_w]; (rh,rw) resized extent (host computes mmcv rescale_size); mean3/std3 are HOST pointers. */
