@@ -956,6 +956,92 @@ def png_decode(files, device=None, stats=None, _infos=None):
     return out[0] if single else out
 
 
+# ---- lossless WebP files to device frames (csrc/webpdec.hip + webpread.py; utils.io_utils.imread_device) -------------------------
+WEBP_DECODE_SCRATCH_BYTES = 64 << 20   # files are decoded in chunks whose scratch stays below this (one file is always taken)
+
+
+def webp_decode(files, device=None, alpha=False, stats=None, _infos=None):
+    """Lossless WebP files (VP8L; contract DESIGN.md §4.15) to device uint8 tensors: [H,W,3] in B, G, R order, equal to
+    utils.io_utils.imread on every byte, or with alpha=True [H,W,4] in B, G, R, A order, equal to PIL's convert('RGBA') (a file whose
+    header says "no alpha" gets A = 255).  `files` is one `bytes` (one tensor is returned) or a list of `bytes` (a list is
+    returned); sizes and features may differ within a call.  The host walks the RIFF container (webpread.probe; a file the decoder
+    does not take -- lossy, animated, rotated -- raises webpread.Unsupported) and uploads only the VP8L chunks' payloads; the
+    entropy decode, the inverse transforms and the colour store run on the device (csm_webp_decode) in chunks of files whose
+    scratch stays below WEBP_DECODE_SCRATCH_BYTES.  A corrupt stream raises CsmError.  A valid file with more prefix-code groups
+    than the cap (webpread.GROUP_CAP, or one per 4 x 4 pixels in a smaller image) raises webpread.Unsupported after the decode,
+    with the indices of such files in its `files` attribute.  The tensors of a chunk are views of one allocation.  `stats` (a
+    dict) receives 'chunks': the number of files of every native call."""
+    import ctypes
+    from . import webpread
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    datas = [files] if single else list(files)
+    for d in datas:
+        if not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError("webp_decode: bytes or a list of bytes expected (got %s)" % type(d).__name__)
+    infos = _infos if _infos is not None else [webpread.probe(d) for d in datas]
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.CsmError("webp_decode: the device must be a GPU (got %s); libcsm355 has no CPU path" % dev)
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    L = _lib.load()
+    words = L.csm_webp_decode_desc_words()
+    assert words == webpread.DESC_WORDS
+    c_desc = ctypes.POINTER(ctypes.c_int32)
+    channels = 4 if alpha else 3
+
+    def scratch_bytes(desc):
+        return L.csm_webp_decode_scratch_bytes(desc.ctypes.data_as(c_desc), i32(desc.shape[0]))
+
+    own = [scratch_bytes(webpread.descriptor(info, 0, 0, channels).reshape(1, -1)) for info in infos]
+    out, chunks, over = [], [], []
+    i = 0
+    while i < len(datas):
+        k, total = 1, own[i]
+        while i + k < len(datas) and total + own[i + k] <= WEBP_DECODE_SCRATCH_BYTES:
+            total += own[i + k]
+            k += 1
+        part = list(zip(datas[i:i + k], infos[i:i + k]))
+        # the blob: every file's VP8L payload on a 16-byte boundary
+        blob_off, o = [], 0
+        for _, info in part:
+            blob_off.append(o)
+            o += (info['payload'][1] - info['payload'][0] + 15) & ~15
+        blob_h = _np.zeros(o, _np.uint8)
+        desc = _np.zeros((k, words), _np.int32)
+        out_off, oo = [], 0
+        for j, (d, info) in enumerate(part):
+            p = webpread.payload(d, info)
+            blob_h[blob_off[j]:blob_off[j] + p.size] = p
+            desc[j] = webpread.descriptor(info, blob_off[j], oo, channels)
+            out_off.append(oo)
+            oo += (info['height'] * info['width'] * channels + 15) & ~15
+        with torch.cuda.device(dev):
+            blob = torch.from_numpy(blob_h).to(dev)
+            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
+            need = scratch_bytes(desc)
+            if need == 0:
+                raise _lib.CsmError("webp_decode: %s" % L.csm_last_error().decode())
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+            info_h = (ctypes.c_int * k)()
+            check(L.csm_webp_decode(ptr(blob), i64(blob.numel()), desc.ctypes.data_as(c_desc), i32(k), ptr(pixels), i64(oo),
+                                    ptr(scratch), info_h, stream_ptr(dev)), "webp_decode")
+        over += [i + j for j in range(k) if info_h[j] & webpread.ERR_CAP]
+        chunks.append(k)
+        for j, (_, info) in enumerate(part):
+            H, W = info['height'], info['width']
+            out.append(pixels[out_off[j]:out_off[j] + H * W * channels].view(H, W, channels))
+        i += k
+    if stats is not None:
+        stats['chunks'] = chunks
+    if over:
+        e = webpread.Unsupported("webp_decode: file(s) %s of the call hold more prefix-code groups than the decoder's cap (%d)"
+                                 % (over, webpread.GROUP_CAP))
+        e.files = tuple(over)
+        raise e
+    return out[0] if single else out
+
+
 # ---- PNG of device images (csrc/png.hip + pngcode.py; utils.io_utils.imwrite, the mask PNGs, video.write_apng) -------------
 PNG_SCRATCH_BYTES = 64 << 20           # images are encoded in chunks whose scratch stays below this (one image is always taken)
 

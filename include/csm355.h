@@ -26,7 +26,7 @@ extern "C" {
 #define CSM_ERR_ARG 1
 #define CSM_ERR_HIP 2
 #define CSM_ERR_NAN 3
-#define CSM_ERR_DATA 4   /* corrupt input data (csm_jpeg_decode, csm_png_decode) */
+#define CSM_ERR_DATA 4   /* corrupt input data (csm_jpeg_decode, csm_png_decode, csm_webp_decode) */
 
 /* thread-local message of the last non-zero status */
 const char *csm_last_error(void);
@@ -652,6 +652,32 @@ size_t csm_png_decode_scratch_bytes(const int32_t *desc_host, int n);
 int csm_png_decode_desc_words(void);
 int csm_png_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
                    void *scratch, int *info_host, void *stream);
+
+/* Lossless WebP files (VP8L) to uint8 B, G, R or B, G, R, A pixels (webpdec.hip; contract DESIGN.md §4.15, restated in
+ * tests/webpdec_restatement.py: the result equals what libwebp decodes on every byte).  The host parses the RIFF container
+ * (cartoonsegmentation_amd/webpread.py) and hands over one blob of device bytes and one descriptor per file; files of different
+ * sizes and features share a call.  Everything the format allows inside a stream is taken (the four transforms in any order, every
+ * sub-image, a colour cache of 1 .. 11 bits, meta prefix codes, simple and normal codes, every backward reference), with one limit:
+ * at most min(2600, ceil(W / 4) * ceil(H / 4)) prefix-code groups per file.
+ * desc_host: host int32 [n][csm_webp_decode_desc_words() = 12]: [0] H, [1] W (each 1 .. 16384, as the five bytes of the VP8L header
+ *   say), [2] the header's alpha flag (0 / 1), [3] the output channels (3: B, G, R; 4: B, G, R, A), [4] [5] offset (a multiple of
+ *   16) and length of the VP8L chunk's payload in the blob, [6] 0, [7] [8] the byte offset of the file's pixels in out (low 31 bits,
+ *   the bits above; a multiple of 4), the rest 0.
+ * out: u8, file i at its offset as [H][W][channels]; A is 255 where the stream's own header says the file has no alpha.  blob, out
+ *   and scratch are 16-byte aligned.
+ * scratch: csm_webp_decode_scratch_bytes(desc_host, n) device bytes (0 for invalid descriptors), a function of the descriptors
+ *   alone: per file 8 B per pixel (two ARGB buffers), 12 B per 4 x 4 block (the three sub-images), 1 KiB of palette, 8992 B per
+ *   group up to the cap (count and direct tables of the five codes, their symbols in canonical order), and 200 B.
+ * csm_webp_decode: info_host (may be NULL) receives n words, the error word of every file (bits as in csrc/csm_vp8l.h).  The call
+ *   SYNCHRONISES the stream once, at the end.  Returns CSM_ERR_DATA for a corrupt stream (an invalid or over-subscribed code, a
+ *   reference before the first or past the last pixel, a second transform of one type, cache bits outside 1 .. 11, a stream that
+ *   ends early, a header that contradicts the descriptor).  A file with more groups than the cap is not corrupt: the call
+ *   returns CSM_OK (unless another file is corrupt), bit 32 of that file's word is set and its pixels are not written.  Whatever the
+ *   data, no read or store leaves the file's own ranges.  No kernel waits on another workgroup; the output is deterministic. */
+size_t csm_webp_decode_scratch_bytes(const int32_t *desc_host, int n);
+int csm_webp_decode_desc_words(void);
+int csm_webp_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
+                    void *scratch, int *info_host, void *stream);
 
 /* The device half of a GIF file (gif.hip; contract DESIGN.md §4.10, restated in tests/gif_restatement.py, byte-identical): one
  * 256-colour palette per clip and the LZW stream (minimum code size 8) of every frame.  1 <= H, W <= 65535.

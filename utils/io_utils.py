@@ -30,7 +30,7 @@ def imread(path):
         return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
 
 
-def imread_device_many(paths, device=None, stats=None, progressive=None):
+def imread_device_many(paths, device=None, stats=None, progressive=None, webp=None):
     """imread for a list of paths with the pixels on the device: a list of uint8 BGR [H,W,3] tensors.  A .jpg / .jpeg file that the
     device decoder takes (cartoonsegmentation_amd.jpegcode.probe: baseline, Huffman, grey or Y Cb Cr at 4:4:4 / 4:2:2 / 4:2:0) and
     whose EXIF orientation is 1 or absent is decoded on the MI355X by ops.jpeg_decode, all such files in one call: only the file's
@@ -44,15 +44,24 @@ def imread_device_many(paths, device=None, stats=None, progressive=None):
     the progressive .jpg / .jpeg files that jpegcode.probe(data, progressive=True) accepts and whose orientation is 1 or absent to
     the device, in the same ops.jpeg_decode call as the baseline ones; rotated progressive files and scan scripts
     that the probe refuses stay with imread.  `stats` then also receives 'jpeg_progressive', the indices of those files, which are
-    listed in 'jpeg' as well."""
+    listed in 'jpeg' as well.
+
+    webp=True (None reads the environment variable CSM_DEVICE_DECODE_WEBP, '1' = on; the default is off) also sends every .webp file
+    that cartoonsegmentation_amd.webpread.probe accepts (lossless, not animated, orientation 1 or absent) to the device
+    (ops.webp_decode, DESIGN.md §4.15: equal to imread on every byte), all such files in one call.  Lossy and animated files, and
+    files with more prefix-code groups than the decoder's cap, stay with imread.  `stats` then also receives 'webp', the indices of
+    the files decoded on the device.  With the option off nothing changes: a .webp path goes through imread."""
     import torch
-    from cartoonsegmentation_amd import jpegcode, ops, pngread
+    from cartoonsegmentation_amd import jpegcode, ops, pngread, webpread
+    if webp is None:
+        webp = os.environ.get('CSM_DEVICE_DECODE_WEBP', '0') == '1'
     if progressive is None:
         progressive = os.environ.get('CSM_DEVICE_DECODE_PROGRESSIVE', '0') == '1'
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     out = [None] * len(paths)
     idx, datas, infos = [], [], []
     pidx, pdatas, pinfos = [], [], []
+    widx, wdatas, winfos = [], [], []
     host = []
     for i, path in enumerate(paths):
         suffix = Path(str(path)).suffix.lower()
@@ -76,6 +85,16 @@ def imread_device_many(paths, device=None, stats=None, progressive=None):
             if info is not None:
                 pidx.append(i); pdatas.append(data); pinfos.append(info)
                 continue
+        elif suffix == '.webp' and webp:
+            with open(path, 'rb') as f:
+                data = f.read()
+            try:
+                info = webpread.probe(data)
+            except webpread.Unsupported:
+                info = None
+            if info is not None:
+                widx.append(i); wdatas.append(data); winfos.append(info)
+                continue
         host.append(i)
         out[i] = torch.from_numpy(imread(path)).to(dev)
     if datas:
@@ -84,16 +103,31 @@ def imread_device_many(paths, device=None, stats=None, progressive=None):
     if pdatas:
         for i, t in zip(pidx, ops.png_decode(pdatas, dev, _infos=pinfos)):
             out[i] = t
+    while wdatas:
+        try:
+            for i, t in zip(widx, ops.webp_decode(wdatas, dev, _infos=winfos)):
+                out[i] = t
+            break
+        except webpread.Unsupported as e:                          # files over the group cap: they go through imread, the rest again
+            if not e.files:
+                raise
+            for j in sorted(e.files, reverse=True):
+                i = widx.pop(j); wdatas.pop(j); winfos.pop(j)
+                host.append(i)
+                out[i] = torch.from_numpy(imread(paths[i])).to(dev)
+            host.sort()
     if stats is not None:
         stats.update(jpeg=idx, png=pidx, host=host)
+        if webp:
+            stats['webp'] = widx
         if progressive:
             stats['jpeg_progressive'] = [i for i, info in zip(idx, infos) if info['progressive']]
     return out
 
 
-def imread_device(path, device=None, progressive=None):
+def imread_device(path, device=None, progressive=None, webp=None):
     """imread with the pixels on the device: see imread_device_many"""
-    return imread_device_many([path], device, progressive=progressive)[0]
+    return imread_device_many([path], device, progressive=progressive, webp=webp)[0]
 
 
 def imwrite(img, file_path, auto_mkdir=True):
