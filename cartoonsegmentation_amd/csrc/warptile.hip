@@ -568,7 +568,12 @@ __global__ __launch_bounds__(kBlock) void k_tile_holes(int H, int W, TileGeom g,
             constexpr int kAhead = 4;            // speculative steps per trip: the positions do not depend on what is read
             {
                 const int ox = __shfl_xor(ix, 16), oy = __shfl_xor(iy, 16);
-                const bool pair_ok = done && ok && (__shfl_xor((int)(done && ok), 16) != 0);
+                // the exchange runs in EVERY lane: behind `found && ...` only the lanes with found == true would execute it, the
+                // compiler may then take the exchanged value for the constant 1, and a found ray whose partner has left the image or
+                // is still marching (ix = iy = 0) would count as a complete pair and make the true winner give up
+                const bool found = done && ok;
+                const bool partner_found = __shfl_xor((int)found, 16) != 0;
+                const bool pair_ok = found && partner_found;
                 const float ddx = (float)(ox - ix), ddy = (float)(oy - iy);
                 float m = pair_ok ? sqrtf(ddx * ddx + ddy * ddy) : INFINITY;
 #pragma unroll
