@@ -47,8 +47,6 @@ struct Plan {
     int64_t o_files, o_state, o_cnt_n, o_cnt_r, o_off_n, o_off_r, o_flag, o_err, o_coef, o_planes, total;
 };
 
-int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 // false: the descriptors are invalid (the error is set)
 bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes, bool check_ranges, Plan &p) {
     if (!desc || n < 1 || n > 65535) { csm::set_error("invalid argument: 1 <= n <= 65535 descriptors"); return false; }
@@ -89,7 +87,7 @@ bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes
             const int h = c == 0 ? f.hs : 1, v = c == 0 ? f.vs : 1;
             f.pw[c] = f.mx * h * 8; f.ph[c] = f.my * v * 8;
             f.plane_off[c] = p.plane_bytes;
-            if (c < f.nc) p.plane_bytes += align16((int64_t)f.pw[c] * f.ph[c]);
+            if (c < f.nc) p.plane_bytes += csm::align16((int64_t)f.pw[c] * f.ph[c]);
         }
         p.nsub += f.nsub;
         p.blocks += nblk;
@@ -98,15 +96,15 @@ bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes
         p.max_pixels = std::max(p.max_pixels, (int64_t)f.H * f.W);
     }
     int64_t o = 0;
-    p.o_files = o;   o += align16((int64_t)n * sizeof(JFile));
-    p.o_state = o;   o += align16(p.nsub * 8);
-    p.o_cnt_n = o;   o += align16(p.nsub * 4);
-    p.o_cnt_r = o;   o += align16(p.nsub * 4);
-    p.o_off_n = o;   o += align16(p.nsub * 8);
-    p.o_off_r = o;   o += align16(p.nsub * 4);
+    p.o_files = o;   o += csm::align16((int64_t)n * sizeof(JFile));
+    p.o_state = o;   o += csm::align16(p.nsub * 8);
+    p.o_cnt_n = o;   o += csm::align16(p.nsub * 4);
+    p.o_cnt_r = o;   o += csm::align16(p.nsub * 4);
+    p.o_off_n = o;   o += csm::align16(p.nsub * 8);
+    p.o_off_r = o;   o += csm::align16(p.nsub * 4);
     p.o_flag = o;    o += 16;
-    p.o_err = o;     o += align16((int64_t)n * 4);
-    p.o_coef = o;    o += align16(p.blocks * 128);
+    p.o_err = o;     o += csm::align16((int64_t)n * 4);
+    p.o_coef = o;    o += csm::align16(p.blocks * 128);
     p.o_planes = o;  o += p.plane_bytes;
     p.total = o;
     return true;

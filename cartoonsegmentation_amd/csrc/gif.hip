@@ -20,6 +20,7 @@
 // Threads OR whole 32-bit words into the zeroed output: integer ORs of disjoint bits, whose order cannot change a byte.  No float
 // atomics, no grid-wide waits, no allocation, no sync; the output is deterministic.
 #include "csm_common.h"
+#include "csm_bits.h"
 
 namespace {
 
@@ -54,8 +55,6 @@ bool make_geo(int n, int H, int W, Geo &g) {
     return g.units < (1 << 24);               // one workgroup per segment covers the batch
 }
 
-int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 struct Scratch {
     uint16_t *codes;       // [units][kSegStride]
     uint32_t *count;       // [units]: codes of the segment
@@ -69,11 +68,11 @@ Scratch make_scratch(const Geo &g, void *base) {
     Scratch s;
     char *p = (char *)base;
     int64_t o = 0;
-    s.codes = (uint16_t *)(p + o);      o += align16(g.units * kSegStride * 2);
-    s.count = (uint32_t *)(p + o);      o += align16(g.units * 4);
-    s.seg_off = (int64_t *)(p + o);     o += align16(g.units * 8);
-    s.frame_bytes = (int64_t *)(p + o); o += align16((int64_t)g.n * 8);
-    s.frame_off = (int64_t *)(p + o);   o += align16((int64_t)g.n * 8);
+    s.codes = (uint16_t *)(p + o);      o += csm::align16(g.units * kSegStride * 2);
+    s.count = (uint32_t *)(p + o);      o += csm::align16(g.units * 4);
+    s.seg_off = (int64_t *)(p + o);     o += csm::align16(g.units * 8);
+    s.frame_bytes = (int64_t *)(p + o); o += csm::align16((int64_t)g.n * 8);
+    s.frame_off = (int64_t *)(p + o);   o += csm::align16((int64_t)g.n * 8);
     s.total = o;
     return s;
 }
@@ -85,23 +84,6 @@ __device__ __forceinline__ int width_after(int m) { return 9 + (m >= 255) + (m >
 // bits of the first m codes of a segment
 __device__ __forceinline__ int code_bits(int m) {
     return 9 * min(m, 255) + 10 * min(max(m - 255, 0), 512) + 11 * min(max(m - 767, 0), 1024) + 12 * max(m - 1791, 0);
-}
-
-// exclusive prefix of v over the workgroup, and the total; sh: kBlock elements of LDS
-__device__ int64_t block_exclusive(int64_t v, int64_t *sh, int64_t &total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const int64_t w = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += w;
-        __syncthreads();
-    }
-    total = sh[kBlock - 1];
-    const int64_t ex = t ? sh[t - 1] : 0;
-    __syncthreads();
-    return ex;
 }
 
 // ---- palette: histogram and mapping -----------------------------------------------------------------------------------------
@@ -230,7 +212,7 @@ __global__ __launch_bounds__(kBlock) void k_gif_offsets(Geo g, const uint32_t *_
     const int per = (g.nseg + kBlock - 1) / kBlock, k0 = min(g.nseg, t * per), k1 = min(g.nseg, k0 + per);
     int64_t sum = 0, total;
     for (int k = k0; k < k1; ++k) sum += (k ? width_after((int)C[k - 1]) : 9) + code_bits((int)C[k]);
-    int64_t ex = block_exclusive(sum, sScan, total);
+    int64_t ex = csm_bits::block_exclusive<kBlock>(sum, sScan, total);
     for (int k = k0; k < k1; ++k) { O[k] = ex; ex += (k ? width_after((int)C[k - 1]) : 9) + code_bits((int)C[k]); }
     if (t == 0) {
         const int64_t b = (total + width_after((int)C[g.nseg - 1]) + 7) >> 3;
@@ -247,31 +229,9 @@ __global__ __launch_bounds__(kBlock) void k_gif_frame_offsets(int n, const int64
     const int per = (n + kBlock - 1) / kBlock, f0 = min(n, t * per), f1 = min(n, f0 + per);
     int64_t sum = 0, total;
     for (int f = f0; f < f1; ++f) sum += (frame_bytes[f] + 3) & ~(int64_t)3;
-    int64_t ex = block_exclusive(sum, sScan, total);
+    int64_t ex = csm_bits::block_exclusive<kBlock>(sum, sScan, total);
     for (int f = f0; f < f1; ++f) { frame_off[f] = ex; ex += (frame_bytes[f] + 3) & ~(int64_t)3; }
 }
-
-// LSB-first bit writer into a zeroed buffer of 32-bit words.  A thread ORs each word it completes once; the words at its two
-// ends are shared with its neighbours.  Nothing is written at or past word `limit`.
-struct BitSink {
-    uint32_t *buf;
-    int64_t w, limit;
-    unsigned long long acc;
-    int fill;
-    __device__ __forceinline__ void open(uint32_t *b, int64_t pos, int64_t lim) { buf = b; w = pos >> 5; fill = (int)(pos & 31); acc = 0; limit = lim; }
-    // the n low bits of v, 0 <= n <= 32
-    __device__ __forceinline__ void put(uint32_t v, int n) {
-        acc |= (unsigned long long)v << fill;
-        fill += n;
-        if (fill >= 32) {
-            if (w < limit) atomicOr(buf + w, (uint32_t)acc);
-            ++w;
-            acc >>= 32;
-            fill -= 32;
-        }
-    }
-    __device__ __forceinline__ void close() { if (fill && w < limit && (uint32_t)acc) atomicOr(buf + w, (uint32_t)acc); fill = 0; acc = 0; }
-};
 
 // one workgroup per segment; thread t writes codes [16 t, 16 t + 16), thread 0 the Clear before them, and the thread that holds
 // the last code of a frame's last segment the EOI behind it
@@ -289,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void k_gif_pack(Geo g, const uint16_t *__re
     const int64_t off = frame_off[f];
     const int64_t limit = min(off + ((frame_bytes[f] + 3) & ~(int64_t)3), out_bytes) >> 2;
     const uint16_t *C = codes + unit * kSegStride;
-    BitSink sink;
+    csm_bits::BitSink sink;
     sink.open((uint32_t *)out, off * 8 + seg_off[unit] + (t ? w0 + code_bits(j0) : 0), limit);
     if (t == 0) sink.put(kClear, w0);
     for (int j = j0; j < j1; ++j) sink.put(C[j], width_after(j));

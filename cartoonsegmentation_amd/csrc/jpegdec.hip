@@ -317,7 +317,7 @@ extern "C" int csm_jpeg_decode(const uint8_t *blob, int64_t blob_bytes, const in
     uint8_t *planes = (uint8_t *)(S + p.o_planes);
     // the descriptors live in p until this call returns, and it returns only after the stream has drained (below)
     CSM_HIP(hipMemcpyAsync(files, p.files.data(), (size_t)n * sizeof(JFile), hipMemcpyHostToDevice, st));
-    CSM_HIP(hipMemsetAsync(flag, 0, (size_t)(p.o_coef - p.o_flag) + (size_t)align16(p.blocks * 128), st));       // flag, err, coefficients
+    CSM_HIP(hipMemsetAsync(flag, 0, (size_t)(p.o_coef - p.o_flag) + (size_t)csm::align16(p.blocks * 128), st));       // flag, err, coefficients
     const dim3 sub_grid((unsigned)p.max_wg, (unsigned)n);
     k_jd_sync_local<<<sub_grid, kLanes, 0, st>>>(blob, files, state, cnt_n, cnt_r);
     int rc = csm::check_launch("k_jd_sync_local"); if (rc) return rc;

@@ -111,13 +111,13 @@ bool make_scan_plan(const Plan &p, const int32_t *sdesc, int n_scans, int64_t bl
         }
     }
     int64_t o = p.total;
-    q.o_scans = o;  o += align16((int64_t)n_scans * sizeof(PScan));
-    q.o_state = o;  o += align16(q.nsub * 8);
-    q.o_cnt_n = o;  o += align16(q.nsub * 4);
-    q.o_cnt_r = o;  o += align16(q.nsub * 4);
-    q.o_off_n = o;  o += align16(q.nsub * 8);
-    q.o_off_r = o;  o += align16(q.nsub * 4);
-    q.o_mask = o;   o += align16(q.masks * 8);
+    q.o_scans = o;  o += csm::align16((int64_t)n_scans * sizeof(PScan));
+    q.o_state = o;  o += csm::align16(q.nsub * 8);
+    q.o_cnt_n = o;  o += csm::align16(q.nsub * 4);
+    q.o_cnt_r = o;  o += csm::align16(q.nsub * 4);
+    q.o_off_n = o;  o += csm::align16(q.nsub * 8);
+    q.o_off_r = o;  o += csm::align16(q.nsub * 4);
+    q.o_mask = o;   o += csm::align16(q.masks * 8);
     q.o_flag = o;   o += 16;
     q.total = o;
     return true;
@@ -648,7 +648,7 @@ extern "C" int csm_jpeg_decode_progressive(const uint8_t *blob, int64_t blob_byt
     // the descriptors live in p and q until this call returns, and it returns only after the stream has drained (below)
     CSM_HIP(hipMemcpyAsync(files, p.files.data(), (size_t)n * sizeof(JFile), hipMemcpyHostToDevice, st));
     CSM_HIP(hipMemcpyAsync(scans, q.scans.data(), (size_t)n_scans * sizeof(PScan), hipMemcpyHostToDevice, st));
-    CSM_HIP(hipMemsetAsync(S + p.o_flag, 0, (size_t)(p.o_coef - p.o_flag) + (size_t)align16(p.blocks * 128), st));   // flag, err, coefficients
+    CSM_HIP(hipMemsetAsync(S + p.o_flag, 0, (size_t)(p.o_coef - p.o_flag) + (size_t)csm::align16(p.blocks * 128), st));   // flag, err, coefficients
     CSM_HIP(hipMemsetAsync(flag, 0, 16, st));
     int passes = 0, levels = 0, rc;
     int i = 0;

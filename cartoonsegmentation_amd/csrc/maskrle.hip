@@ -20,6 +20,7 @@
 //   write:   k_rle_write (each unit writes its characters at its offset)
 // Scratch is n * W * S * 28 bytes; nothing is proportional to the number of counts, and no pass uses atomics (deterministic).
 #include "csm_common.h"
+#include "csm_bits.h"
 
 namespace {
 
@@ -123,23 +124,6 @@ __global__ __launch_bounds__(kBlock) void k_rle_units(const uint8_t *__restrict_
     area[u.idx] = set;
 }
 
-// exclusive prefix of v over the block (and the block total); sh: kBlock int64 of LDS
-__device__ int64_t block_exclusive_i64(int64_t v, int64_t *sh, int64_t &total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const int64_t w = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += w;
-        __syncthreads();
-    }
-    total = sh[kBlock - 1];
-    const int64_t ex = t ? sh[t - 1] : 0;
-    __syncthreads();
-    return ex;
-}
-
 // one block per instance: each thread folds a run of consecutive units, the block scans the runs, then each thread rewrites its
 // units with the carry of everything before them.  info[inst] = {num_counts, -, area, -}.
 __global__ __launch_bounds__(kBlock) void k_rle_carry_scan(int64_t U, int4 *__restrict__ carry, const int *__restrict__ area,
@@ -165,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void k_rle_carry_scan(int64_t U, int4 *__re
     Carry ex = t ? load_carry(sc + t - 1) : Carry{0, 0, 0, 0};
     const int total = sc[kBlock - 1].x;
     int64_t set_total;
-    block_exclusive_i64(set, sa, set_total);
+    csm_bits::block_exclusive<kBlock>(set, sa, set_total);
     for (int64_t u = u0; u < u1; ++u) {
         const Carry c = load_carry(C + u);
         store_carry(C + u, ex);
@@ -205,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void k_rle_char_scan(int64_t U, int64_t *__
     for (int64_t u = u0; u < u1; ++u) sum += Ch[u];
     __shared__ int64_t sh[kBlock];
     int64_t total;
-    int64_t ex = block_exclusive_i64(sum, sh, total);
+    int64_t ex = csm_bits::block_exclusive<kBlock>(sum, sh, total);
     for (int64_t u = u0; u < u1; ++u) { const int64_t v = Ch[u]; Ch[u] = ex; ex += v; }
     if (t == 0) info[4 * inst + 1] = total;
 }
@@ -218,7 +202,7 @@ __global__ __launch_bounds__(kBlock) void k_rle_instance_offsets(int n, int64_t 
     for (int i = i0; i < i1; ++i) sum += info[4 * i + 1];
     __shared__ int64_t sh[kBlock];
     int64_t total;
-    int64_t ex = block_exclusive_i64(sum, sh, total);
+    int64_t ex = csm_bits::block_exclusive<kBlock>(sum, sh, total);
     for (int i = i0; i < i1; ++i) { info[4 * i + 3] = ex; ex += info[4 * i + 1]; }
 }
 

@@ -16,6 +16,7 @@
 // worst case does not fit, in a slot of the scratch.  Threads OR whole 32-bit words into the zeroed buffer: integer ORs of disjoint
 // bits, whose order cannot change a byte.  No float atomics, no grid-wide waits; the output is deterministic.
 #include "csm_common.h"
+#include "csm_bits.h"
 #include <cstring>
 
 namespace {
@@ -121,8 +122,6 @@ int64_t units_per_launch(const Geo &g) {
     return std::max<int64_t>(1, std::min<int64_t>(g.units, kRowSlotBudget / row_slot_bytes(g)));
 }
 
-int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 struct Scratch {
     int16_t *coef;         // [units][bpr][64], zigzag order
     int64_t *row_off;      // [units]: offset of the row's segment inside its frame
@@ -135,9 +134,9 @@ Scratch make_scratch(const Geo &g, void *base) {
     Scratch s;
     char *p = (char *)base;
     int64_t o = 0;
-    s.coef = (int16_t *)(p + o);     o += align16(g.units * g.bpr * 128);
-    s.row_off = (int64_t *)(p + o);  o += align16(g.units * 8);
-    s.row_bytes = (int *)(p + o);    o += align16(g.units * 4);
+    s.coef = (int16_t *)(p + o);     o += csm::align16(g.units * g.bpr * 128);
+    s.row_off = (int64_t *)(p + o);  o += csm::align16(g.units * 8);
+    s.row_bytes = (int *)(p + o);    o += csm::align16(g.units * 4);
     s.slots = (uint32_t *)(p + o);   o += rows_in_lds(g) ? 0 : units_per_launch(g) * row_slot_bytes(g);
     s.total = o;
     return s;
@@ -247,23 +246,6 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_transform(const uint8_t *__rest
 }
 
 // ---- segment pass -----------------------------------------------------------------------------------------------------------
-// exclusive prefix of v over the workgroup, and the total; sh: kBlock elements of LDS
-template <typename T> __device__ T block_exclusive(T v, T *sh, T &total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const T w = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += w;
-        __syncthreads();
-    }
-    total = sh[kBlock - 1];
-    const T ex = t ? sh[t - 1] : 0;
-    __syncthreads();
-    return ex;
-}
-
 // MSB-first bit writer into a zeroed buffer of 32-bit words (word w holds the stream's bytes 4w..4w+3, first byte on top).  A
 // thread ORs each word it completes once; the words at its two ends are shared with its neighbours.
 template <bool EMIT> struct BitSink {
@@ -373,7 +355,7 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_rows(const int16_t *__restrict_
         mybits += len.bits;
     }
     int total_bits;
-    const int start = block_exclusive(mybits, sScan, total_bits);
+    const int start = csm_bits::block_exclusive<kBlock>(mybits, sScan, total_bits);
     const int nbytes = (total_bits + 7) >> 3, nwords = (nbytes + 3) >> 2;
     if (nwords > slot_words) return;                  // cannot happen (kBlockBytes is the worst case); never write past the buffer
 
@@ -400,7 +382,7 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_rows(const int16_t *__restrict_
     int ff = 0;
     for (int i = i0; i < i1; ++i) ff += stream_byte<LDS>(buf, i) == 0xFFu;
     int total_ff;
-    const int ff_before = block_exclusive(ff, sScan, total_ff);
+    const int ff_before = csm_bits::block_exclusive<kBlock>(ff, sScan, total_ff);
     const bool last_row = r == g.my - 1;
     const int seg = nbytes + total_ff + (last_row ? 0 : 2);
     if constexpr (!WRITE) {
@@ -434,7 +416,7 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_row_offsets(int my, const int *
     int64_t *O = row_off + (int64_t)f * my;
     int64_t sum = 0, total;
     for (int r = r0; r < r1; ++r) sum += B[r];
-    int64_t ex = kHeaderBytes + block_exclusive(sum, sScan, total);
+    int64_t ex = kHeaderBytes + csm_bits::block_exclusive<kBlock>(sum, sScan, total);
     for (int r = r0; r < r1; ++r) { O[r] = ex; ex += B[r]; }
     if (t == 0) info[2 * f + 1] = kHeaderBytes + total + 2;
 }
@@ -446,7 +428,7 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_frame_offsets(int n, int64_t *_
     const int per = (n + kBlock - 1) / kBlock, f0 = min(n, t * per), f1 = min(n, f0 + per);
     int64_t sum = 0, total;
     for (int f = f0; f < f1; ++f) sum += info[2 * f + 1];
-    int64_t ex = block_exclusive(sum, sh, total);
+    int64_t ex = csm_bits::block_exclusive<kBlock>(sum, sh, total);
     for (int f = f0; f < f1; ++f) { info[2 * f] = ex; ex += info[2 * f + 1]; }
 }
 

@@ -17,10 +17,14 @@
 // Threads OR whole 32-bit words into the zeroed output: integer ORs of disjoint bits, whose order cannot change a byte.  No float
 // atomics, no grid-wide waits, no allocation, no sync; the output is deterministic.
 #include "csm_common.h"
+#include "csm_bits.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using csm_bits::BitSink;
+using csm_bits::parse_chunk;
+
+constexpr int kBlock = 256;                  // threads of every workgroup: the size csm_bits.h's helpers are instantiated for
 constexpr uint32_t kAdlerMod = 65521;
 constexpr int kSyms = 286;                   // literal / length alphabet
 constexpr int kEob = 256;
@@ -59,8 +63,6 @@ bool make_geo(int n, int H, int W, int C, int flags, Geo &g) {
     return (int64_t)H * g.L < INT32_MAX && g.units < (1 << 24);
 }
 
-int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 struct Scratch {
     uint8_t *filt;         // [units][L]: filtered scanlines
     int64_t *row_off;      // [units]: bit offset of the scanline's symbols behind the block header
@@ -73,61 +75,13 @@ Scratch make_scratch(const Geo &g, void *base) {
     Scratch s;
     char *p = (char *)base;
     int64_t o = 0;
-    s.filt = (uint8_t *)(p + o);      o += align16(g.units * g.L);
-    s.row_off = (int64_t *)(p + o);   o += align16(g.units * 8);
-    s.row_bits = (uint32_t *)(p + o); o += align16(g.units * 4);
-    s.ad_a = (uint32_t *)(p + o);     o += align16(g.units * 4);
-    s.ad_b = (uint32_t *)(p + o);     o += align16(g.units * 4);
+    s.filt = (uint8_t *)(p + o);      o += csm::align16(g.units * g.L);
+    s.row_off = (int64_t *)(p + o);   o += csm::align16(g.units * 8);
+    s.row_bits = (uint32_t *)(p + o); o += csm::align16(g.units * 4);
+    s.ad_a = (uint32_t *)(p + o);     o += csm::align16(g.units * 4);
+    s.ad_b = (uint32_t *)(p + o);     o += csm::align16(g.units * 4);
     s.total = o;
     return s;
-}
-
-// ---- workgroup helpers ------------------------------------------------------------------------------------------------------
-// sum of v over the workgroup, in every thread; sh: kBlock elements of LDS
-template <typename T> __device__ T block_sum(T v, T *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = kBlock >> 1; d > 0; d >>= 1) {
-        if (t < d) sh[t] += sh[t + d];
-        __syncthreads();
-    }
-    const T r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-// exclusive prefix of v over the workgroup, and the total; sh: kBlock elements of LDS
-template <typename T> __device__ T block_exclusive(T v, T *sh, T &total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const T w = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += w;
-        __syncthreads();
-    }
-    total = sh[kBlock - 1];
-    const T ex = t ? sh[t - 1] : 0;
-    __syncthreads();
-    return ex;
-}
-
-// minimum of v over the threads AFTER this one (`none` for the last); sh: kBlock elements of LDS
-__device__ int block_min_after(int v, int none, int *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const int w = t + d < kBlock ? sh[t + d] : none;
-        __syncthreads();
-        sh[t] = min(sh[t], w);
-        __syncthreads();
-    }
-    const int r = t + 1 < kBlock ? sh[t + 1] : none;
-    __syncthreads();
-    return r;
 }
 
 // ---- filter pass ------------------------------------------------------------------------------------------------------------
@@ -172,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void k_png_filter(const uint8_t *__restrict
     int type = 0, best = 0;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const int v = block_sum(s[k], sInt);
+        const int v = csm_bits::block_sum<kBlock>(s[k], sInt);
         if (k == 0 || v < best) { best = v; type = k; }      // ties go to the lowest type
     }
     uint8_t *F = filt + unit * g.L;
@@ -191,8 +145,8 @@ __global__ __launch_bounds__(kBlock) void k_png_filter(const uint8_t *__restrict
         A += (unsigned)v;
         B += (unsigned long long)(g.L - 1 - j) * (unsigned)v;
     }
-    A = block_sum(A, sLong);
-    B = block_sum(B, sLong);
+    A = csm_bits::block_sum<kBlock>(A, sLong);
+    B = csm_bits::block_sum<kBlock>(B, sLong);
     if (t == 0) { ad_a[unit] = (uint32_t)(A % kAdlerMod); ad_b[unit] = (uint32_t)(B % kAdlerMod); }
 }
 
@@ -210,9 +164,9 @@ __global__ __launch_bounds__(kBlock) void k_png_adler(Geo g, const uint32_t *__r
         sb += B[k];
         sw += (unsigned long long)A[k] * (unsigned)(g.H - 1 - k) % kAdlerMod;
     }
-    sa = block_sum(sa, sLong);
-    sb = block_sum(sb, sLong);
-    sw = block_sum(sw, sLong);
+    sa = csm_bits::block_sum<kBlock>(sa, sLong);
+    sb = csm_bits::block_sum<kBlock>(sb, sLong);
+    sw = csm_bits::block_sum<kBlock>(sw, sLong);
     if (t == 0) {
         const unsigned long long Lm = (unsigned)g.L % kAdlerMod;
         const unsigned long long s1 = (1 + sa) % kAdlerMod;
@@ -234,28 +188,6 @@ __device__ __forceinline__ uint32_t length_entry(int len) {
     const int sym = 261 + 4 * e + ((m >> e) & 3);
     return (uint32_t)sym | (uint32_t)e << 16 | (uint32_t)(m & ((1 << e) - 1)) << 24;
 }
-
-// LSB-first bit writer into a zeroed buffer of 32-bit words.  A thread ORs each word it completes once; the words at its two
-// ends are shared with its neighbours.  Nothing is written at or past word `limit`.
-struct BitSink {
-    uint32_t *buf;
-    int64_t w, limit;
-    unsigned long long acc;
-    int fill;
-    __device__ __forceinline__ void open(uint32_t *b, int64_t pos, int64_t lim) { buf = b; w = pos >> 5; fill = (int)(pos & 31); acc = 0; limit = lim; }
-    // the n low bits of v, 0 <= n <= 32
-    __device__ __forceinline__ void put(uint32_t v, int n) {
-        acc |= (unsigned long long)v << fill;
-        fill += n;
-        if (fill >= 32) {
-            if (w < limit) atomicOr(buf + w, (uint32_t)acc);
-            ++w;
-            acc >>= 32;
-            fill -= 32;
-        }
-    }
-    __device__ __forceinline__ void close() { if (fill && w < limit && (uint32_t)acc) atomicOr(buf + w, (uint32_t)acc); fill = 0; acc = 0; }
-};
 
 // what one run of `len` equal bytes v costs or emits: the literal, (len - 1) / 258 matches of 258, then one match of the
 // remainder if that is 3 or more, else the remainder as literals.  code[s] = reversed code | length << 16.
@@ -292,20 +224,6 @@ template <int MODE> struct RunSink {
     }
 };
 
-// the runs that START in [i0, i1) of the scanline F[0, L); next = the first run start at or after i1 (L if none)
-template <int MODE> __device__ __forceinline__ void parse_chunk(const uint8_t *__restrict__ F, int i0, int i1, int first, int next,
-                                                                 RunSink<MODE> &rs) {
-    int s = first;
-    while (s < i1) {
-        const int v = F[s];
-        int e = s + 1;
-        while (e < i1 && F[e] == v) ++e;
-        if (e == i1) e = next;                              // the run goes on to the next start (which may be i1 itself)
-        rs.run(v, e - s);
-        s = e;
-    }
-}
-
 // One workgroup per scanline.  Every thread takes a stretch of consecutive bytes and the runs that start there.
 //   kHist: counts into table[f][0..285] (device table of the measure call)
 //   kBits: row_bits[unit] under the code of host[f]
@@ -324,19 +242,13 @@ __global__ __launch_bounds__(kBlock) void k_png_parse(const uint8_t *__restrict_
     const uint32_t *T = MODE == kHist ? nullptr : host + (int64_t)f * kTabWords;
     for (int i = t; i < kSyms; i += kBlock) sTab[i] = MODE == kHist ? 0u : T[i];
 
-    const int per = (g.L + kBlock - 1) / kBlock, i0 = min(g.L, t * per), i1 = min(g.L, i0 + per);
-    int first = g.L;                                        // the first run start of this thread's stretch
-    for (int i = i0; i < i1; ++i) {
-        if (i == 0 || F[i] != F[i - 1]) { first = i; break; }
-    }
-    const int next = block_min_after(first, g.L, sScan);    // (its barriers also publish sTab)
-    if (first >= i1) first = i1;
+    const csm_bits::RunStretch my = csm_bits::run_stretch<kBlock>(F, g.L, sScan);   // (its barriers also publish sTab)
 
     RunSink<MODE> rs;
     rs.hist = sTab; rs.code = sTab; rs.bits = 0;
     rs.dist_bits = MODE == kHist ? 0 : (int)T[kTabDistBits];
     if constexpr (MODE == kHist) {
-        parse_chunk(F, i0, i1, first, next, rs);
+        parse_chunk(F, my, rs);
         __syncthreads();
         uint32_t *G = table + (int64_t)f * kMeasureWords;
         for (int i = t; i < kSyms; i += kBlock) if (sTab[i]) atomicAdd(G + i, sTab[i]);
@@ -344,11 +256,11 @@ __global__ __launch_bounds__(kBlock) void k_png_parse(const uint8_t *__restrict_
         {
             RunSink<kBits> len;
             len.hist = nullptr; len.code = sTab; len.bits = 0; len.dist_bits = rs.dist_bits;
-            parse_chunk(F, i0, i1, first, next, len);
+            parse_chunk(F, my, len);
             rs.bits = len.bits;
         }
         int total;
-        const int start = block_exclusive((int)rs.bits, sScan, total);
+        const int start = csm_bits::block_exclusive<kBlock>((int)rs.bits, sScan, total);
         if constexpr (MODE == kBits) {
             if (t == 0) row_bits[unit] = (uint32_t)total;
         } else {
@@ -357,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void k_png_parse(const uint8_t *__restrict_
             uint32_t *O = (uint32_t *)(out + off);
             const int64_t base = (int64_t)T[kTabHdrBits] + row_off[unit];
             rs.sink.open(O, base + start, limit);
-            parse_chunk(F, i0, i1, first, next, rs);
+            parse_chunk(F, my, rs);
             rs.sink.close();
             if (r == 0) {
                 const int hw = min(kHdrWordsMax, ((int)T[kTabHdrBits] + 31) >> 5);
@@ -385,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void k_png_row_offsets(int H, const uint32_
     int64_t *O = row_off + (int64_t)f * H;
     int64_t sum = 0, total;
     for (int r = r0; r < r1; ++r) sum += B[r];
-    int64_t ex = block_exclusive(sum, sScan, total);
+    int64_t ex = csm_bits::block_exclusive<kBlock>(sum, sScan, total);
     for (int r = r0; r < r1; ++r) { O[r] = ex; ex += B[r]; }
 }
 

@@ -58,17 +58,15 @@ struct Plan {
     int64_t o_files, o_flags, o_err, o_res, total;
 };
 
-int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 // false: the descriptors are invalid (the error is set)
 bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes, bool check_ranges, Plan &p) {
     if (!desc || n < 1 || n > 65535) { csm::set_error("invalid argument: 1 <= n <= 65535 descriptors"); return false; }
     p.files.resize(n);
     int64_t o = 0;
-    p.o_files = o;  o += align16((int64_t)n * sizeof(PFile));
-    p.o_flags = o;  o += align16((int64_t)n * kFlagWords * 4);
-    p.o_err = o;    o += align16((int64_t)n * 4);
-    p.o_res = o;    o += align16((int64_t)n * 16);
+    p.o_files = o;  o += csm::align16((int64_t)n * sizeof(PFile));
+    p.o_flags = o;  o += csm::align16((int64_t)n * kFlagWords * 4);
+    p.o_err = o;    o += csm::align16((int64_t)n * 4);
+    p.o_res = o;    o += csm::align16((int64_t)n * 16);
     for (int i = 0; i < n; ++i) {
         const int32_t *d = desc + (int64_t)i * kDescWords;
         PFile &f = p.files[i];
@@ -81,7 +79,7 @@ bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes
         const int64_t stride = 1 + (int64_t)f.W * f.bpp, raw = ok ? stride * f.H : 0;
         ok = ok && raw <= kMaxRaw;
         if (ok && check_ranges) {
-            ok = align16((int64_t)f.in_off + f.in_len) <= blob_bytes && (int64_t)f.pal_off + 768 <= blob_bytes &&
+            ok = csm::align16((int64_t)f.in_off + f.in_len) <= blob_bytes && (int64_t)f.pal_off + 768 <= blob_bytes &&
                  f.out_off + (int64_t)f.H * f.W * 3 <= out_bytes;
         }
         if (!ok) { csm::set_error("invalid argument: descriptor %d of the PNG decode", i); return false; }
@@ -89,10 +87,10 @@ bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes
         f.nchunks = (int)((raw + kChunk - 1) / kChunk);
         f.rounds = 0;
         while (f.rounds < kMaxRounds && ((int64_t)1 << f.rounds) < raw) ++f.rounds;
-        f.lit_off = o;    o += align16(raw);
-        f.src_off = o;    o += align16(raw * 4);
-        f.match_off = o;  o += align16((int64_t)f.match_cap * 8);
-        f.part_off = o;   o += align16((int64_t)f.nchunks * 8);
+        f.lit_off = o;    o += csm::align16(raw);
+        f.src_off = o;    o += csm::align16(raw * 4);
+        f.match_off = o;  o += csm::align16((int64_t)f.match_cap * 8);
+        f.part_off = o;   o += csm::align16((int64_t)f.nchunks * 8);
         p.max_raw = std::max(p.max_raw, f.raw);
         p.max_rounds = std::max(p.max_rounds, f.rounds);
     }

@@ -25,6 +25,7 @@
 #include "csm_common.h"
 #include "csm_vp8_tables.h"
 #include "csm_boolenc.h"
+#include "csm_bits.h"
 
 namespace {
 
@@ -62,8 +63,6 @@ bool make_geo(int n, int H, int W, Geo &g) {
     return true;
 }
 
-int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 struct Scratch {
     uint8_t *src, *rec;        // [n][ypx + 2 cpx]: Y, U, V of every frame
     int16_t *levels;           // [n][nmb][25][16], zigzag order: Y2, 16 Y, 4 U, 4 V
@@ -81,17 +80,17 @@ Scratch make_scratch(const Geo &g, void *base) {
     char *p = (char *)base;
     int64_t o = 0;
     const int64_t frame = g.ypx + 2 * g.cpx, n = g.n;
-    s.src = (uint8_t *)(p + o);      o += align16(n * frame);
-    s.rec = (uint8_t *)(p + o);      o += align16(n * frame);
-    s.levels = (int16_t *)(p + o);   o += align16(n * g.nmb * 800);
-    s.nz = (uint32_t *)(p + o);      o += align16(n * g.nmb * 4);
-    s.modes = (uint8_t *)(p + o);    o += align16(n * g.nmb);
-    s.nskip = (uint32_t *)(p + o);   o += align16(n * 4 + 4);
+    s.src = (uint8_t *)(p + o);      o += csm::align16(n * frame);
+    s.rec = (uint8_t *)(p + o);      o += csm::align16(n * frame);
+    s.levels = (int16_t *)(p + o);   o += csm::align16(n * g.nmb * 800);
+    s.nz = (uint32_t *)(p + o);      o += csm::align16(n * g.nmb * 4);
+    s.modes = (uint8_t *)(p + o);    o += csm::align16(n * g.nmb);
+    s.nskip = (uint32_t *)(p + o);   o += csm::align16(n * 4 + 4);
     s.status = s.nskip + n;
-    s.sizes = (int64_t *)(p + o);    o += align16((int64_t)g.units * 8);
-    s.offs = (int64_t *)(p + o);     o += align16((int64_t)g.units * 8);
-    s.first = (uint8_t *)(p + o);    o += align16(n * g.first_cap);
-    s.part = (uint8_t *)(p + o);     o += align16(n * g.parts * g.part_cap);
+    s.sizes = (int64_t *)(p + o);    o += csm::align16((int64_t)g.units * 8);
+    s.offs = (int64_t *)(p + o);     o += csm::align16((int64_t)g.units * 8);
+    s.first = (uint8_t *)(p + o);    o += csm::align16(n * g.first_cap);
+    s.part = (uint8_t *)(p + o);     o += csm::align16(n * g.parts * g.part_cap);
     s.total = o;
     return s;
 }
@@ -522,23 +521,6 @@ __global__ __launch_bounds__(64) void k_webp_code(Geo g, int qi, const int16_t *
     if (e.over) atomicOr(status, 1u);
 }
 
-// exclusive prefix of v over the workgroup, and the total; sh: kBlock elements of LDS
-__device__ int64_t block_exclusive(int64_t v, int64_t *sh, int64_t &total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const int64_t w = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += w;
-        __syncthreads();
-    }
-    total = sh[kBlock - 1];
-    const int64_t ex = t ? sh[t - 1] : 0;
-    __syncthreads();
-    return ex;
-}
-
 // one workgroup: offs[u] = the bytes of the units before u; info[u] = (offset, bytes), info[units] = (status, total)
 __global__ __launch_bounds__(kBlock) void k_webp_offsets(int units, const int64_t *__restrict__ sizes, const uint32_t *__restrict__ status,
                                                           int64_t *__restrict__ offs, int64_t *__restrict__ info) {
@@ -547,7 +529,7 @@ __global__ __launch_bounds__(kBlock) void k_webp_offsets(int units, const int64_
     const int per = (units + kBlock - 1) / kBlock, u0 = min(units, t * per), u1 = min(units, u0 + per);
     int64_t sum = 0, total;
     for (int u = u0; u < u1; ++u) sum += sizes[u];
-    int64_t ex = block_exclusive(sum, sScan, total);
+    int64_t ex = csm_bits::block_exclusive<kBlock>(sum, sScan, total);
     for (int u = u0; u < u1; ++u) { offs[u] = ex; info[2 * u] = ex; info[2 * u + 1] = sizes[u]; ex += sizes[u]; }
     if (t == 0) { info[2 * units] = *status; info[2 * units + 1] = total; }
 }

@@ -47,15 +47,13 @@ struct Plan {
     int64_t o_files, o_res, total;
 };
 
-int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 // false: the descriptors are invalid (the error is set)
 bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes, bool check_ranges, Plan &p) {
     if (!desc || n < 1 || n > 65535) { csm::set_error("invalid argument: 1 <= n <= 65535 descriptors"); return false; }
     p.files.resize(n);
     int64_t o = 0;
-    p.o_files = o;  o += align16((int64_t)n * sizeof(WFile));
-    p.o_res = o;    o += align16((int64_t)n * sizeof(vp::Result));
+    p.o_files = o;  o += csm::align16((int64_t)n * sizeof(WFile));
+    p.o_res = o;    o += csm::align16((int64_t)n * sizeof(vp::Result));
     for (int i = 0; i < n; ++i) {
         const int32_t *d = desc + (int64_t)i * kDescWords;
         WFile &f = p.files[i];
@@ -70,13 +68,13 @@ bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes
         f.sub_cap = vp::subsample((uint32_t)f.W, 2) * vp::subsample((uint32_t)f.H, 2);
         f.group_cap = std::min(vp::kGroupCap, f.sub_cap);
         f.res_off = p.o_res + (int64_t)i * sizeof(vp::Result);
-        f.argb_off[0] = o;  o += align16(pixels * 4);
-        f.argb_off[1] = o;  o += align16(pixels * 4);
-        f.pred_off = o;     o += align16((int64_t)f.sub_cap * 4);
-        f.colour_off = o;   o += align16((int64_t)f.sub_cap * 4);
-        f.meta_off = o;     o += align16((int64_t)f.sub_cap * 4);
+        f.argb_off[0] = o;  o += csm::align16(pixels * 4);
+        f.argb_off[1] = o;  o += csm::align16(pixels * 4);
+        f.pred_off = o;     o += csm::align16((int64_t)f.sub_cap * 4);
+        f.colour_off = o;   o += csm::align16((int64_t)f.sub_cap * 4);
+        f.meta_off = o;     o += csm::align16((int64_t)f.sub_cap * 4);
         f.pal_off = o;      o += 1024;
-        f.group_off = o;    o += align16((int64_t)f.group_cap * sizeof(vp::Group));
+        f.group_off = o;    o += csm::align16((int64_t)f.group_cap * sizeof(vp::Group));
         p.max_pixels = std::max(p.max_pixels, pixels);
     }
     p.total = o;

@@ -15,10 +15,14 @@
 // LSB-first; the host hands the prefix codes over bit-reversed.  Threads OR whole 32-bit words into the zeroed output: integer ORs
 // of disjoint bits, whose order cannot change a byte.  No float atomics, no grid-wide waits, no allocation, no sync.
 #include "csm_common.h"
+#include "csm_bits.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using csm_bits::BitSink;
+using csm_bits::parse_chunk;
+
+constexpr int kBlock = 256;                              // threads of every workgroup: the size csm_bits.h's helpers are instantiated for
 constexpr int kBlkBits = 4, kBlk = 1 << kBlkBits;        // kBlk * kBlk == kBlock: one thread per pixel of a block
 constexpr int kModes = 13;
 constexpr int kMaxRef = 4096;
@@ -40,8 +44,6 @@ constexpr int kDescWords = 8;
 enum { dPtr = 0, dH = 1, dW = 2, dChan = 3, dPix = 4, dBlk = 5, dUnit = 6 };
 
 enum { kHist = 0, kBits = 1, kEmit = 2 };
-
-int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 struct Plan {
     int64_t pixels, blocks, units;       // of all images: residual pixels, 16 x 16 blocks, rows of both planes
@@ -70,46 +72,12 @@ bool make_plan(int64_t *desc, int n, bool fill, void *base, Plan &p) {
     p.pixels = pix; p.blocks = blk; p.units = unit;
     char *b = (char *)base;
     int64_t o = 0;
-    p.res = (uint32_t *)(b + o);      o += align16(pix * 4);
-    p.modes = (uint32_t *)(b + o);    o += align16(blk * 4);
-    p.row_bits = (uint32_t *)(b + o); o += align16(unit * 4);
-    p.row_off = (int64_t *)(b + o);   o += align16(unit * 8);
+    p.res = (uint32_t *)(b + o);      o += csm::align16(pix * 4);
+    p.modes = (uint32_t *)(b + o);    o += csm::align16(blk * 4);
+    p.row_bits = (uint32_t *)(b + o); o += csm::align16(unit * 4);
+    p.row_off = (int64_t *)(b + o);   o += csm::align16(unit * 8);
     p.total = o;
     return true;
-}
-
-// ---- workgroup helpers (as in png.hip) ----------------------------------------------------------------------------------------
-// exclusive prefix of v over the workgroup, and the total; sh: kBlock elements of LDS
-template <typename T> __device__ T block_exclusive(T v, T *sh, T &total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const T w = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += w;
-        __syncthreads();
-    }
-    total = sh[kBlock - 1];
-    const T ex = t ? sh[t - 1] : 0;
-    __syncthreads();
-    return ex;
-}
-
-// minimum of v over the threads AFTER this one (`none` for the last); sh: kBlock elements of LDS
-__device__ int block_min_after(int v, int none, int *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const int w = t + d < kBlock ? sh[t + d] : none;
-        __syncthreads();
-        sh[t] = min(sh[t], w);
-        __syncthreads();
-    }
-    const int r = t + 1 < kBlock ? sh[t + 1] : none;
-    __syncthreads();
-    return r;
 }
 
 // the image whose first block / row unit (desc word `field`) is the last one not above u
@@ -250,28 +218,6 @@ __device__ __forceinline__ uint32_t length_entry(int len) {
     return (uint32_t)(2 * hb + ((v >> eb) & 1)) | (uint32_t)eb << 8 | (uint32_t)(v & ((1 << eb) - 1)) << 16;
 }
 
-// LSB-first bit writer into a zeroed buffer of 32-bit words (as in png.hip).  A thread ORs each word it completes once; the
-// words at its two ends are shared with its neighbours.  Nothing is written at or past word `limit`.
-struct BitSink {
-    uint32_t *buf;
-    int64_t w, limit;
-    unsigned long long acc;
-    int fill;
-    __device__ __forceinline__ void open(uint32_t *b, int64_t pos, int64_t lim) { buf = b; w = pos >> 5; fill = (int)(pos & 31); acc = 0; limit = lim; }
-    // the n low bits of v, 0 <= n <= 32
-    __device__ __forceinline__ void put(uint32_t v, int n) {
-        acc |= (unsigned long long)v << fill;
-        fill += n;
-        if (fill >= 32) {
-            if (w < limit && (uint32_t)acc) atomicOr(buf + w, (uint32_t)acc);
-            ++w;
-            acc >>= 32;
-            fill -= 32;
-        }
-    }
-    __device__ __forceinline__ void close() { if (fill && w < limit && (uint32_t)acc) atomicOr(buf + w, (uint32_t)acc); fill = 0; acc = 0; }
-};
-
 // what one run of `len` equal pixels v costs or emits: four literals, (len - 1) / 4096 references of 4096, then one reference of
 // the remainder if there is one.  code[s] = reversed code | length << 16; a length of 0 (the one symbol of a simple code) costs
 // and writes nothing.
@@ -308,20 +254,6 @@ template <int MODE> struct RunSink {
     }
 };
 
-// the runs that START in [i0, i1) of the row F[0, L); next = the first run start at or after i1 (L if none)
-template <int MODE> __device__ __forceinline__ void parse_chunk(const uint32_t *__restrict__ F, int i0, int i1, int first, int next,
-                                                                 RunSink<MODE> &rs) {
-    int s = first;
-    while (s < i1) {
-        const uint32_t v = F[s];
-        int e = s + 1;
-        while (e < i1 && F[e] == v) ++e;
-        if (e == i1) e = next;                              // the run goes on to the next start (which may be i1 itself)
-        rs.run(v, e - s);
-        s = e;
-    }
-}
-
 // One workgroup per row of a plane.  Every thread takes a stretch of consecutive pixels and the runs that start there.
 //   kHist: counts into table[plane][0..1087] (device table of the measure call)
 //   kBits: row_bits[unit] under the codes of host[plane]
@@ -346,18 +278,12 @@ __global__ __launch_bounds__(kBlock) void k_ll_parse(const int64_t *__restrict__
     const uint32_t *T = MODE == kHist ? nullptr : host + pl * kTabWords;
     for (int i = t; i < kSyms; i += kBlock) sTab[i] = MODE == kHist ? 0u : T[i];
 
-    const int per = (L + kBlock - 1) / kBlock, i0 = min(L, t * per), i1 = min(L, i0 + per);
-    int first = L;                                          // the first run start of this thread's stretch
-    for (int i = i0; i < i1; ++i) {
-        if (i == 0 || F[i] != F[i - 1]) { first = i; break; }
-    }
-    const int next = block_min_after(first, L, sScan);      // (its barriers also publish sTab)
-    if (first >= i1) first = i1;
+    const csm_bits::RunStretch my = csm_bits::run_stretch<kBlock>(F, L, sScan);     // (its barriers also publish sTab)
 
     RunSink<MODE> rs;
     rs.hist = sTab; rs.code = sTab; rs.bits = 0;
     if constexpr (MODE == kHist) {
-        parse_chunk(F, i0, i1, first, next, rs);
+        parse_chunk(F, my, rs);
         __syncthreads();
         uint32_t *G = table + pl * kSyms;
         for (int i = t; i < kSyms; i += kBlock) if (sTab[i]) atomicAdd(G + i, sTab[i]);
@@ -365,11 +291,11 @@ __global__ __launch_bounds__(kBlock) void k_ll_parse(const int64_t *__restrict__
         {
             RunSink<kBits> len;
             len.hist = nullptr; len.code = sTab; len.bits = 0;
-            parse_chunk(F, i0, i1, first, next, len);
+            parse_chunk(F, my, len);
             rs.bits = len.bits;
         }
         int total;
-        const int start = block_exclusive((int)rs.bits, sScan, total);
+        const int start = csm_bits::block_exclusive<kBlock>((int)rs.bits, sScan, total);
         if constexpr (MODE == kBits) {
             if (t == 0) row_bits[unit] = (uint32_t)total;
         } else {
@@ -379,7 +305,7 @@ __global__ __launch_bounds__(kBlock) void k_ll_parse(const int64_t *__restrict__
             uint32_t *O = (uint32_t *)(out + off);
             const int64_t base = ((int64_t)T[kTabStartLo] | (int64_t)T[kTabStartHi] << 32) + row_off[unit];
             rs.sink.open(O, base + start, limit);
-            parse_chunk(F, i0, i1, first, next, rs);
+            parse_chunk(F, my, rs);
             rs.sink.close();
             if (row == 0) {
                 const int64_t w0 = T[kTabHdrWord];
@@ -404,7 +330,7 @@ __global__ __launch_bounds__(kBlock) void k_ll_row_offsets(const int64_t *__rest
     int64_t *O = row_off + u0;
     int64_t sum = 0, total;
     for (int r = r0; r < r1; ++r) sum += B[r];
-    int64_t ex = block_exclusive(sum, sScan, total);
+    int64_t ex = csm_bits::block_exclusive<kBlock>(sum, sScan, total);
     for (int r = r0; r < r1; ++r) { O[r] = ex; ex += B[r]; }
 }
 

@@ -627,6 +627,123 @@ def mask_rle_encode(masks):
     return counts, info_h[:, 2].copy()
 
 
+# ---- host scaffolding the codec wrappers below share ------------------------------------------------------------------------
+def _byte_files(files, what):
+    """(single, datas): one `bytes`-like file, or a list of them"""
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    datas = [files] if single else list(files)
+    for d in datas:
+        if not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError("%s: bytes or a list of bytes expected (got %s)" % (what, type(d).__name__))
+    return single, datas
+
+
+def _gpu_device(device, what):
+    """`device` (None: the current one) as torch.device('cuda', index)"""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.CsmError("%s: the device must be a GPU (got %s); libcsm355 has no CPU path" % (what, dev))
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    return dev
+
+
+def _budget_chunks(own, budget):
+    """(i, k) for runs of k consecutive items from i whose sizes own[i] ... sum to at most `budget`; one item is always taken"""
+    i = 0
+    while i < len(own):
+        k, total = 1, own[i]
+        while i + k < len(own) and total + own[i + k] <= budget:
+            total += own[i + k]
+            k += 1
+        yield i, k
+        i += k
+
+
+def _check_sides(what, H, W):
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError("%s: H and W must be in [1, 65535] (got %dx%d)" % (what, H, W))
+
+
+def _image_batch(frames, what, size_check):
+    """The acceptance rule of png_streams and the GIF route: device uint8 [n,H,W], [H,W] (grey), [n,H,W,3], [H,W,3] (colour; a
+    uint8 tensor of rank 3 whose last dimension is 3 is one colour image) or bool [n,H,W], [H,W] (masks).  Returns (contiguous
+    uint8 tensor [n,H,W] or [n,H,W,3], colour, mask); size_check(H, W, channels) runs before the device is looked at."""
+    if not isinstance(frames, torch.Tensor):
+        raise _lib.CsmError("%s: frames must be a device tensor (got %s)" % (what, type(frames).__name__))
+    shape, mask = tuple(frames.shape), frames.dtype == torch.bool
+    if mask:
+        ok, colour = frames.dim() in (2, 3), False
+    else:
+        colour = frames.dim() == 4 or (frames.dim() == 3 and shape[-1] == 3)
+        ok = frames.dtype == torch.uint8 and (frames.dim() in (2, 3) or (frames.dim() == 4 and shape[-1] == 3))
+    if not ok:
+        raise _lib.CsmError("%s: uint8 [n,H,W], [H,W], [n,H,W,3], [H,W,3] or bool [n,H,W], [H,W] expected (got %s %s)"
+                            % (what, frames.dtype, shape))
+    lead = 0 if frames.dim() == (3 if colour else 2) else 1
+    size_check(int(shape[lead]), int(shape[lead + 1]), 3 if colour else 1)
+    if not frames.is_cuda:
+        raise _lib.CsmError("%s: frames must be a device tensor; libcsm355 has no CPU path" % what)
+    im = frames.contiguous()
+    im = im.view(torch.uint8) if mask else im
+    return (im if lead else im.unsqueeze(0)), colour, mask
+
+
+def _bgr_frames(frames, what, size_check):
+    """The acceptance rule of jpeg_encode and webp_streams: device uint8 frames [n,H,W,3] or one [H,W,3], returned contiguous as
+    [n,H,W,3]; size_check(H, W) runs before the device is looked at."""
+    if not isinstance(frames, torch.Tensor):
+        raise _lib.CsmError("%s: frames must be a device tensor (got %s)" % (what, type(frames).__name__))
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise _lib.CsmError("%s: uint8 frames [n,H,W,3] or [H,W,3] expected (got %s %s)" % (what, frames.dtype, tuple(frames.shape)))
+    size_check(*(int(v) for v in frames.shape[-3:-1]))
+    if not frames.is_cuda:
+        raise _lib.CsmError("%s: frames must be a device tensor; libcsm355 has no CPU path" % what)
+    fr = frames.contiguous()
+    return fr.unsqueeze(0) if fr.dim() == 3 else fr
+
+
+def _decode_groups(what, call, datas, infos, dev, budget, channels, layout, scratch_fn, decode_fn, info_per_file=False):
+    """The chunked-call driver of the decoders: files (datas[i], infos[i]) go to the native decoder in groups of consecutive files
+    whose scratch stays below `budget` (one file is always taken).  The format supplies
+      layout(part, out_off) -> (blob bytes, descriptor tables, fill): for the files `part` = [(data, info)], whose pixels begin at
+        out_off[j] of the group's output, the size of the blob to upload, the host int32 tables the native calls take (in their
+        order; each is passed as pointer, rows) and fill(blob_h), which writes the blob; layout is also called for each file
+        alone, to size that file's scratch, so everything costly belongs in fill;
+      scratch_fn(*tables) and decode_fn(blob, blob bytes, *tables, out, out bytes, scratch, info_host, stream): the native pair.
+    Yields (i, k, info_h, tensors) per group: its first file and file count, the ints the native call returned (one per file with
+    info_per_file, else 4) and the files' [H,W,channels] tensors, views of one allocation."""
+    import ctypes
+    c_desc = ctypes.POINTER(ctypes.c_int32)
+
+    def args(tables):
+        return [a for t in tables for a in (t.ctypes.data_as(c_desc), i32(t.shape[0]))]
+
+    own = [scratch_fn(*args(layout([item], [0])[1])) for item in zip(datas, infos)]
+    for i, k in _budget_chunks(own, budget):
+        part = list(zip(datas[i:i + k], infos[i:i + k]))
+        out_off, oo = [], 0                                  # every file's pixels begin on a 16-byte boundary of one allocation
+        for _, info in part:
+            out_off.append(oo)
+            oo += (info['height'] * info['width'] * channels + 15) & ~15
+        blob_bytes, tables, fill = layout(part, out_off)     # `tables` named: alive while table_args points into them
+        table_args = args(tables)
+        blob_h = _np.zeros(blob_bytes, _np.uint8)
+        fill(blob_h)
+        with torch.cuda.device(dev):
+            blob = torch.from_numpy(blob_h).to(dev)
+            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
+            need = scratch_fn(*table_args)
+            if need == 0:
+                raise _lib.CsmError("%s: %s" % (what, _lib.load().csm_last_error().decode()))
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+            info_h = (ctypes.c_int * (k if info_per_file else 4))()
+            check(decode_fn(ptr(blob), i64(blob.numel()), *table_args, ptr(pixels), i64(oo), ptr(scratch), info_h, stream_ptr(dev)),
+                  call)
+        yield i, k, info_h, [pixels[o:o + info['height'] * info['width'] * channels].view(info['height'], info['width'], channels)
+                             for o, (_, info) in zip(out_off, part)]
+
+
 # ---- baseline JPEG of device frames (csrc/mjpeg.hip; the frames of video.write_mjpeg_avi) ---------------------------------
 JPEG_SCRATCH_BYTES = 64 << 20          # frames are encoded in chunks whose scratch stays below this (one frame is always taken)
 
@@ -643,14 +760,9 @@ def jpeg_encode(frames, quality=90, subsampling='420'):
         raise ValueError("jpeg_encode: subsampling must be '420' or '444' (got %r)" % (subsampling,))
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
         raise _lib.CsmError("jpeg_encode: frames must be a device tensor; libcsm355 has no CPU path")
-    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
-        raise _lib.CsmError("jpeg_encode: uint8 frames [n,H,W,3] or [H,W,3] expected (got %s %s)" % (frames.dtype, tuple(frames.shape)))
-    fr = frames.contiguous()                                # named: alive until the kernels that read it are enqueued
-    if fr.dim() == 3:
-        fr = fr.unsqueeze(0)
+    # named: alive until the kernels that read it are enqueued
+    fr = _bgr_frames(frames, "jpeg_encode", lambda H, W: _check_sides("jpeg_encode", H, W))
     n, H, W = (int(v) for v in fr.shape[:3])
-    if not (1 <= H <= 65535 and 1 <= W <= 65535):
-        raise ValueError("jpeg_encode: H and W must be in [1, 65535] (got %dx%d)" % (H, W))
     L, dev, st = _lib.load(), fr.device, stream_ptr(fr.device)
     q, sub = i32(int(quality)), i32(int(subsampling))
     per_frame = L.csm_jpeg_scratch_bytes(i32(1), i32(H), i32(W), sub)
@@ -691,22 +803,14 @@ def jpeg_decode(files, device=None, stats=None, _infos=None, progressive=False):
     order of `files`.  `stats` then also receives 'progressive' (the indices of the progressive files), 'levels' (the dependency
     levels launched for every progressive chunk) and 'progressive_passes'."""
     from . import jpegcode
-    single = isinstance(files, (bytes, bytearray, memoryview))
-    datas = [files] if single else list(files)
-    for d in datas:
-        if not isinstance(d, (bytes, bytearray, memoryview)):
-            raise TypeError("jpeg_decode: bytes or a list of bytes expected (got %s)" % type(d).__name__)
+    single, datas = _byte_files(files, "jpeg_decode")
     if _infos is not None:
         infos = _infos
     elif progressive:
         infos = [jpegcode.probe(d, progressive=True) for d in datas]
     else:
         infos = [jpegcode.probe(d) for d in datas]
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.CsmError("jpeg_decode: the device must be a GPU (got %s); libcsm355 has no CPU path" % dev)
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _gpu_device(device, "jpeg_decode")
     L = _lib.load()
     prog = [i for i, info in enumerate(infos) if info.get('progressive')]
     if prog and not progressive:
@@ -731,86 +835,52 @@ def jpeg_decode(files, device=None, stats=None, _infos=None, progressive=False):
     return out[0] if single else out
 
 
-def _jpeg_chunks(own):
-    """runs of consecutive files whose scratch (own[i] bytes each) stays below JPEG_DECODE_SCRATCH_BYTES; one file is always taken"""
-    i = 0
-    while i < len(own):
-        k, total = 1, own[i]
-        while i + k < len(own) and total + own[i + k] <= JPEG_DECODE_SCRATCH_BYTES:
-            total += own[i + k]
-            k += 1
-        yield i, k
-        i += k
-
-
 def _jpeg_decode_baseline(L, datas, infos, dev):
-    import ctypes
     from . import jpegcode
-    words = L.csm_jpeg_decode_desc_words()
+    words, tab = L.csm_jpeg_decode_desc_words(), jpegcode.FILE_TABLE_BYTES
     assert words == jpegcode.DESC_WORDS
-    c_desc = ctypes.POINTER(ctypes.c_int32)
 
-    def scratch_bytes(desc):
-        return L.csm_jpeg_decode_scratch_bytes(desc.ctypes.data_as(c_desc), i32(desc.shape[0]))
-
-    own = [scratch_bytes(jpegcode.descriptor(info, 0, 0, 0).reshape(1, -1)) for info in infos]
-    out, passes = [], []
-    for i, k in _jpeg_chunks(own):
-        part = list(zip(datas[i:i + k], infos[i:i + k]))
+    def layout(part, out_off):
         # the blob: every file's table region, then every file's entropy bytes, each on a 16-byte boundary
-        ent_off, o = [], k * jpegcode.FILE_TABLE_BYTES
+        ent_off, o = [], len(part) * tab
         for _, info in part:
             ent_off.append(o)
             o += (info['entropy'][1] - info['entropy'][0] + 15) & ~15
-        blob_h = _np.zeros(max(o, 16), _np.uint8)
-        desc = _np.zeros((k, words), _np.int32)
-        out_off, oo = [], 0
-        for j, (d, info) in enumerate(part):
-            blob_h[j * jpegcode.FILE_TABLE_BYTES:(j + 1) * jpegcode.FILE_TABLE_BYTES] = jpegcode.file_tables(info)
-            s, e = info['entropy']
-            blob_h[ent_off[j]:ent_off[j] + e - s] = _np.frombuffer(d, _np.uint8, e - s, s)
-            desc[j] = jpegcode.descriptor(info, ent_off[j], j * jpegcode.FILE_TABLE_BYTES, oo)
-            out_off.append(oo)
-            oo += (info['height'] * info['width'] * 3 + 15) & ~15
-        with torch.cuda.device(dev):
-            blob = torch.from_numpy(blob_h).to(dev)
-            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
-            need = scratch_bytes(desc)
-            if need == 0:
-                raise _lib.CsmError("jpeg_decode: %s" % L.csm_last_error().decode())
-            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-            info_h = (ctypes.c_int * 4)()
-            check(L.csm_jpeg_decode(ptr(blob), i64(blob.numel()), desc.ctypes.data_as(c_desc), i32(k), ptr(pixels), i64(oo),
-                                    ptr(scratch), info_h, stream_ptr(dev)), "jpeg_decode")
-        passes.append(int(info_h[0]))
+        desc = _np.zeros((len(part), words), _np.int32)
         for j, (_, info) in enumerate(part):
-            H, W = info['height'], info['width']
-            out.append(pixels[out_off[j]:out_off[j] + H * W * 3].view(H, W, 3))
+            desc[j] = jpegcode.descriptor(info, ent_off[j], j * tab, out_off[j])
+
+        def fill(blob_h):
+            for j, (d, info) in enumerate(part):
+                blob_h[j * tab:(j + 1) * tab] = jpegcode.file_tables(info)
+                s, e = info['entropy']
+                blob_h[ent_off[j]:ent_off[j] + e - s] = _np.frombuffer(d, _np.uint8, e - s, s)
+        return max(o, 16), (desc,), fill
+
+    out, passes = [], []
+    for _, _, info_h, tensors in _decode_groups("jpeg_decode", "jpeg_decode", datas, infos, dev, JPEG_DECODE_SCRATCH_BYTES, 3, layout,
+                                                L.csm_jpeg_decode_scratch_bytes, L.csm_jpeg_decode):
+        passes.append(int(info_h[0]))
+        out += tensors
     return out, passes
 
 
 def _jpeg_decode_progressive(L, datas, infos, dev):
     """the progressive files of jpeg_decode: (tensors, levels per chunk, synchronisation passes per chunk)"""
-    import ctypes
     from . import jpegcode
-    words, swords = L.csm_jpeg_decode_desc_words(), L.csm_jpeg_decode_scan_desc_words()
+    words, swords, tab = L.csm_jpeg_decode_desc_words(), L.csm_jpeg_decode_scan_desc_words(), jpegcode.FILE_TABLE_BYTES
     assert words == jpegcode.DESC_WORDS and swords == jpegcode.SCAN_DESC_WORDS
-    c_desc = ctypes.POINTER(ctypes.c_int32)
     a16 = lambda v: (v + 15) & ~15
 
-    def layout(part):
+    def layout(part, out_off):
         """the blob of a chunk: every file's table region (its quantisation tables), then per scan its decode tables, its entropy
         bytes and, for a refinement with restart markers, where its intervals begin, each on a 16-byte boundary"""
-        k = len(part)
-        o = k * jpegcode.FILE_TABLE_BYTES
+        o = len(part) * tab
         pieces, rows = [], []
-        desc = _np.zeros((k, words), _np.int32)
-        out_off, oo = [], 0
+        desc = _np.zeros((len(part), words), _np.int32)
         for j, (d, info) in enumerate(part):
             head = dict(info, restart_interval=0, components=[dict(c, td=0, ta=0) for c in info['components']], huffman={}, entropy=(0, 0))
-            desc[j] = jpegcode.descriptor(head, 0, j * jpegcode.FILE_TABLE_BYTES, oo)
-            out_off.append(oo)
-            oo += a16(info['height'] * info['width'] * 3)
+            desc[j] = jpegcode.descriptor(head, 0, j * tab, out_off[j])
             level_of = {s: lv for lv, ss in enumerate(jpegcode.scan_levels(info)) for s in ss}
             tabs = jpegcode.scan_tables(info)
             for si, sc in enumerate(info['scans']):
@@ -833,49 +903,28 @@ def _jpeg_decode_progressive(L, datas, infos, dev):
                     pieces.append((o, iv.view(_np.uint8)))
                     o += a16(iv.size * 4)
                 rows.append(jpegcode.scan_descriptor(info, si, j, ent_off, tab_off, level_of[si], iv_off))
-        return o, pieces, desc, _np.stack(rows), out_off, oo
+
+        def fill(blob_h):
+            for j, (_, info) in enumerate(part):
+                blob_h[j * tab:(j + 1) * tab] = quant_only(info)
+            for at, arr in pieces:
+                blob_h[at:at + arr.size] = arr
+        return max(o, 16), (desc, _np.stack(rows)), fill
 
     def quant_only(info):
-        t = _np.zeros(jpegcode.FILE_TABLE_BYTES, _np.uint8)
+        t = _np.zeros(tab, _np.uint8)
         q = _np.zeros((3, 64), _np.uint16)
         for i, c in enumerate(info['components']):
             q[i, list(jpegcode.ZIGZAG)] = info['qtables'][c['tq']]
         t[jpegcode.HUFF_SLOTS * jpegcode.TABLE_BYTES:] = q.view(_np.uint8).ravel()
         return t
 
-    def scratch_bytes(desc, sdesc):
-        return L.csm_jpeg_decode_progressive_scratch_bytes(desc.ctypes.data_as(c_desc), i32(desc.shape[0]),
-                                                           sdesc.ctypes.data_as(c_desc), i32(sdesc.shape[0]))
-
-    own = []
-    for d, info in zip(datas, infos):
-        _, _, desc, sdesc, _, _ = layout([(d, info)])
-        own.append(scratch_bytes(desc, sdesc))
     out, levels, passes = [], [], []
-    for i, k in _jpeg_chunks(own):
-        part = list(zip(datas[i:i + k], infos[i:i + k]))
-        o, pieces, desc, sdesc, out_off, oo = layout(part)
-        blob_h = _np.zeros(max(o, 16), _np.uint8)
-        for j, (_, info) in enumerate(part):
-            blob_h[j * jpegcode.FILE_TABLE_BYTES:(j + 1) * jpegcode.FILE_TABLE_BYTES] = quant_only(info)
-        for at, arr in pieces:
-            blob_h[at:at + arr.size] = arr
-        with torch.cuda.device(dev):
-            blob = torch.from_numpy(blob_h).to(dev)
-            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
-            need = scratch_bytes(desc, sdesc)
-            if need == 0:
-                raise _lib.CsmError("jpeg_decode: %s" % L.csm_last_error().decode())
-            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-            info_h = (ctypes.c_int * 4)()
-            check(L.csm_jpeg_decode_progressive(ptr(blob), i64(blob.numel()), desc.ctypes.data_as(c_desc), i32(k),
-                                                sdesc.ctypes.data_as(c_desc), i32(sdesc.shape[0]), ptr(pixels), i64(oo),
-                                                ptr(scratch), info_h, stream_ptr(dev)), "jpeg_decode_progressive")
+    for _, _, info_h, tensors in _decode_groups("jpeg_decode", "jpeg_decode_progressive", datas, infos, dev, JPEG_DECODE_SCRATCH_BYTES, 3,
+                                                layout, L.csm_jpeg_decode_progressive_scratch_bytes, L.csm_jpeg_decode_progressive):
         passes.append(int(info_h[0]))
         levels.append(int(info_h[1]))
-        for j, (_, info) in enumerate(part):
-            H, W = info['height'], info['width']
-            out.append(pixels[out_off[j]:out_off[j] + H * W * 3].view(H, W, 3))
+        out += tensors
     return out, levels, passes
 
 
@@ -892,65 +941,35 @@ def png_decode(files, device=None, stats=None, _infos=None):
     (csm_png_decode) in chunks of files whose scratch stays below PNG_DECODE_SCRATCH_BYTES.  A corrupt stream (invalid deflate
     data, a wrong Adler-32, a filter type above 4) raises CsmError.  The tensors of a chunk are views of one allocation.  `stats`
     (a dict) receives 'rounds': per chunk, the pointer-doubling rounds (launched, that did work)."""
-    import ctypes
     from . import pngread
-    single = isinstance(files, (bytes, bytearray, memoryview))
-    datas = [files] if single else list(files)
-    for d in datas:
-        if not isinstance(d, (bytes, bytearray, memoryview)):
-            raise TypeError("png_decode: bytes or a list of bytes expected (got %s)" % type(d).__name__)
+    single, datas = _byte_files(files, "png_decode")
     infos = _infos if _infos is not None else [pngread.probe(d) for d in datas]
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.CsmError("png_decode: the device must be a GPU (got %s); libcsm355 has no CPU path" % dev)
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _gpu_device(device, "png_decode")
     L = _lib.load()
     words = L.csm_png_decode_desc_words()
     assert words == pngread.DESC_WORDS
-    c_desc = ctypes.POINTER(ctypes.c_int32)
 
-    def scratch_bytes(desc):
-        return L.csm_png_decode_scratch_bytes(desc.ctypes.data_as(c_desc), i32(desc.shape[0]))
-
-    own = [scratch_bytes(pngread.descriptor(info, 0, 0, 0).reshape(1, -1)) for info in infos]
-    out, rounds = [], []
-    i = 0
-    while i < len(datas):
-        k, total = 1, own[i]
-        while i + k < len(datas) and total + own[i + k] <= PNG_DECODE_SCRATCH_BYTES:
-            total += own[i + k]
-            k += 1
-        part = list(zip(datas[i:i + k], infos[i:i + k]))
-        i += k
+    def layout(part, out_off):
         # the blob: every file's palette (768 bytes), then every file's zlib stream, each on a 16-byte boundary and padded to one
-        stream_off, o = [], k * 768
+        stream_off, o = [], len(part) * 768
         for _, info in part:
             stream_off.append(o)
             o += (info['stream_bytes'] + 15) & ~15
-        blob_h = _np.zeros(o, _np.uint8)
-        desc = _np.zeros((k, words), _np.int32)
-        out_off, oo = [], 0
-        for j, (d, info) in enumerate(part):
-            blob_h[j * 768:(j + 1) * 768] = info['palette'].reshape(-1)
-            blob_h[stream_off[j]:stream_off[j] + info['stream_bytes']] = pngread.zlib_stream(d, info)
-            desc[j] = pngread.descriptor(info, stream_off[j], j * 768, oo)
-            out_off.append(oo)
-            oo += (info['height'] * info['width'] * 3 + 15) & ~15
-        with torch.cuda.device(dev):
-            blob = torch.from_numpy(blob_h).to(dev)
-            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
-            need = scratch_bytes(desc)
-            if need == 0:
-                raise _lib.CsmError("png_decode: %s" % L.csm_last_error().decode())
-            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-            info_h = (ctypes.c_int * 4)()
-            check(L.csm_png_decode(ptr(blob), i64(blob.numel()), desc.ctypes.data_as(c_desc), i32(k), ptr(pixels), i64(oo),
-                                   ptr(scratch), info_h, stream_ptr(dev)), "png_decode")
-        rounds.append((int(info_h[0]), int(info_h[1])))
+        desc = _np.zeros((len(part), words), _np.int32)
         for j, (_, info) in enumerate(part):
-            H, W = info['height'], info['width']
-            out.append(pixels[out_off[j]:out_off[j] + H * W * 3].view(H, W, 3))
+            desc[j] = pngread.descriptor(info, stream_off[j], j * 768, out_off[j])
+
+        def fill(blob_h):
+            for j, (d, info) in enumerate(part):
+                blob_h[j * 768:(j + 1) * 768] = info['palette'].reshape(-1)
+                blob_h[stream_off[j]:stream_off[j] + info['stream_bytes']] = pngread.zlib_stream(d, info)
+        return o, (desc,), fill
+
+    out, rounds = [], []
+    for _, _, info_h, tensors in _decode_groups("png_decode", "png_decode", datas, infos, dev, PNG_DECODE_SCRATCH_BYTES, 3, layout,
+                                                L.csm_png_decode_scratch_bytes, L.csm_png_decode):
+        rounds.append((int(info_h[0]), int(info_h[1])))
+        out += tensors
     if stats is not None:
         stats['rounds'] = rounds
     return out[0] if single else out
@@ -971,67 +990,37 @@ def webp_decode(files, device=None, alpha=False, stats=None, _infos=None):
     than the cap (webpread.GROUP_CAP, or one per 4 x 4 pixels in a smaller image) raises webpread.Unsupported after the decode,
     with the indices of such files in its `files` attribute.  The tensors of a chunk are views of one allocation.  `stats` (a
     dict) receives 'chunks': the number of files of every native call."""
-    import ctypes
     from . import webpread
-    single = isinstance(files, (bytes, bytearray, memoryview))
-    datas = [files] if single else list(files)
-    for d in datas:
-        if not isinstance(d, (bytes, bytearray, memoryview)):
-            raise TypeError("webp_decode: bytes or a list of bytes expected (got %s)" % type(d).__name__)
+    single, datas = _byte_files(files, "webp_decode")
     infos = _infos if _infos is not None else [webpread.probe(d) for d in datas]
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.CsmError("webp_decode: the device must be a GPU (got %s); libcsm355 has no CPU path" % dev)
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _gpu_device(device, "webp_decode")
     L = _lib.load()
     words = L.csm_webp_decode_desc_words()
     assert words == webpread.DESC_WORDS
-    c_desc = ctypes.POINTER(ctypes.c_int32)
     channels = 4 if alpha else 3
 
-    def scratch_bytes(desc):
-        return L.csm_webp_decode_scratch_bytes(desc.ctypes.data_as(c_desc), i32(desc.shape[0]))
-
-    own = [scratch_bytes(webpread.descriptor(info, 0, 0, channels).reshape(1, -1)) for info in infos]
-    out, chunks, over = [], [], []
-    i = 0
-    while i < len(datas):
-        k, total = 1, own[i]
-        while i + k < len(datas) and total + own[i + k] <= WEBP_DECODE_SCRATCH_BYTES:
-            total += own[i + k]
-            k += 1
-        part = list(zip(datas[i:i + k], infos[i:i + k]))
+    def layout(part, out_off):
         # the blob: every file's VP8L payload on a 16-byte boundary
         blob_off, o = [], 0
         for _, info in part:
             blob_off.append(o)
             o += (info['payload'][1] - info['payload'][0] + 15) & ~15
-        blob_h = _np.zeros(o, _np.uint8)
-        desc = _np.zeros((k, words), _np.int32)
-        out_off, oo = [], 0
-        for j, (d, info) in enumerate(part):
-            p = webpread.payload(d, info)
-            blob_h[blob_off[j]:blob_off[j] + p.size] = p
-            desc[j] = webpread.descriptor(info, blob_off[j], oo, channels)
-            out_off.append(oo)
-            oo += (info['height'] * info['width'] * channels + 15) & ~15
-        with torch.cuda.device(dev):
-            blob = torch.from_numpy(blob_h).to(dev)
-            pixels = torch.empty(oo, dtype=torch.uint8, device=dev)
-            need = scratch_bytes(desc)
-            if need == 0:
-                raise _lib.CsmError("webp_decode: %s" % L.csm_last_error().decode())
-            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-            info_h = (ctypes.c_int * k)()
-            check(L.csm_webp_decode(ptr(blob), i64(blob.numel()), desc.ctypes.data_as(c_desc), i32(k), ptr(pixels), i64(oo),
-                                    ptr(scratch), info_h, stream_ptr(dev)), "webp_decode")
+        desc = _np.zeros((len(part), words), _np.int32)
+        for j, (_, info) in enumerate(part):
+            desc[j] = webpread.descriptor(info, blob_off[j], out_off[j], channels)
+
+        def fill(blob_h):
+            for j, (d, info) in enumerate(part):
+                p = webpread.payload(d, info)
+                blob_h[blob_off[j]:blob_off[j] + p.size] = p
+        return o, (desc,), fill
+
+    out, chunks, over = [], [], []
+    for i, k, info_h, tensors in _decode_groups("webp_decode", "webp_decode", datas, infos, dev, WEBP_DECODE_SCRATCH_BYTES, channels,
+                                                layout, L.csm_webp_decode_scratch_bytes, L.csm_webp_decode, info_per_file=True):
         over += [i + j for j in range(k) if info_h[j] & webpread.ERR_CAP]
         chunks.append(k)
-        for j, (_, info) in enumerate(part):
-            H, W = info['height'], info['width']
-            out.append(pixels[out_off[j]:out_off[j] + H * W * channels].view(H, W, channels))
-        i += k
+        out += tensors
     if stats is not None:
         stats['chunks'] = chunks
     if over:
@@ -1051,23 +1040,14 @@ def png_streams(images, bgr=True):
     returns (streams, width, height, colour_type)."""
     if not (isinstance(images, torch.Tensor) and images.is_cuda):
         raise _lib.CsmError("png_encode: images must be a device tensor; libcsm355 has no CPU path")
-    shape, mask = tuple(images.shape), images.dtype == torch.bool
-    if mask:
-        ok, colour = images.dim() in (2, 3), False
-    else:
-        colour = images.dim() == 4 or (images.dim() == 3 and shape[-1] == 3)
-        ok = images.dtype == torch.uint8 and (images.dim() in (2, 3) or (images.dim() == 4 and shape[-1] == 3))
-    if not ok:
-        raise _lib.CsmError("png_encode: uint8 [n,H,W], [H,W], [n,H,W,3], [H,W,3] or bool [n,H,W], [H,W] expected (got %s %s)"
-                            % (images.dtype, shape))
-    im = images.contiguous()                                # named: alive until the kernels that read it are enqueued
-    im = im.view(torch.uint8) if mask else im
-    if im.dim() == (3 if colour else 2):
-        im = im.unsqueeze(0)
+
+    def size_check(H, W, C):
+        if not (1 <= H <= 65535 and 1 <= W <= 65535) or H * (W * C + 1) >= 2 ** 31:
+            raise ValueError("png_encode: H and W must be in [1, 65535] and H * (W * channels + 1) below 2^31 (got %dx%d)" % (H, W))
+
+    im, colour, mask = _image_batch(images, "png_encode", size_check)    # im named: alive until the kernels that read it are enqueued
     n, H, W = (int(v) for v in im.shape[:3])
     C = 3 if colour else 1
-    if not (1 <= H <= 65535 and 1 <= W <= 65535) or H * (W * C + 1) >= 2 ** 31:
-        raise ValueError("png_encode: H and W must be in [1, 65535] and H * (W * channels + 1) below 2^31 (got %dx%d)" % (H, W))
     from . import pngcode
     L, dev, st = _lib.load(), im.device, stream_ptr(im.device)
     flags = i32((1 if colour and bgr else 0) | (2 if mask else 0))
@@ -1126,18 +1106,9 @@ def webp_streams(frames, quality=90):
     quality, can exceed it and then raises ValueError after the chunk's measure call, before any bytes are copied."""
     from . import webpcode
     quality = webpcode.check_quality(quality, "webp_streams")
-    if not isinstance(frames, torch.Tensor):
-        raise _lib.CsmError("webp_streams: frames must be a device tensor (got %s)" % type(frames).__name__)
-    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
-        raise _lib.CsmError("webp_streams: uint8 frames [n,H,W,3] or [H,W,3] expected (got %s %s)" % (frames.dtype, tuple(frames.shape)))
-    H, W = (int(v) for v in frames.shape[-3:-1])
-    webpcode.check_size(W, H, "webp_streams")
-    if not frames.is_cuda:
-        raise _lib.CsmError("webp_streams: frames must be a device tensor; libcsm355 has no CPU path")
-    fr = frames.contiguous()                                # named: alive until the kernels that read it are enqueued
-    if fr.dim() == 3:
-        fr = fr.unsqueeze(0)
-    n = int(fr.shape[0])
+    # named: alive until the kernels that read it are enqueued
+    fr = _bgr_frames(frames, "webp_streams", lambda H, W: webpcode.check_size(W, H, "webp_streams"))
+    n, H, W = (int(v) for v in fr.shape[:3])
     L, dev, st = _lib.load(), fr.device, stream_ptr(fr.device)
     q, units = i32(quality), webpcode.partitions(H) + 1
     per_frame = L.csm_webp_scratch_bytes(i32(1), i32(H), i32(W))
@@ -1244,14 +1215,9 @@ def webp_encode_lossless(images):
         return desc, need
 
     own = [descriptors([it])[1] for it in items]
-    out, i = [], 0
-    while i < len(items):
-        k, total = 1, own[i]
-        while i + k < len(items) and total + own[i + k] <= WEBPLL_SCRATCH_BYTES:
-            total += own[i + k]
-            k += 1
+    out = []
+    for i, k in _budget_chunks(own, WEBPLL_SCRATCH_BYTES):
         part = items[i:i + k]
-        i += k
         desc, need = descriptors(part)
         desc_h = desc.ctypes.data_as(c_desc)
         desc_d = torch.from_numpy(desc).to(dev)
@@ -1465,30 +1431,6 @@ def draw_instances(img, masks, bboxes, colors=None, indices=None, draw_bbox=True
 GIF_SCRATCH_BYTES = 64 << 20           # frames are coded in chunks whose scratch stays below this (one frame is always taken)
 
 
-def _gif_frames(frames, what):
-    """the acceptance rule of ops.png_streams: (uint8 tensor [n,H,W] or [n,H,W,3], colour, mask)"""
-    if not isinstance(frames, torch.Tensor):
-        raise _lib.CsmError("%s: frames must be a device tensor (got %s)" % (what, type(frames).__name__))
-    shape, mask = tuple(frames.shape), frames.dtype == torch.bool
-    if mask:
-        ok, colour = frames.dim() in (2, 3), False
-    else:
-        colour = frames.dim() == 4 or (frames.dim() == 3 and shape[-1] == 3)
-        ok = frames.dtype == torch.uint8 and (frames.dim() in (2, 3) or (frames.dim() == 4 and shape[-1] == 3))
-    if not ok:
-        raise _lib.CsmError("%s: uint8 [n,H,W], [H,W], [n,H,W,3], [H,W,3] or bool [n,H,W], [H,W] expected (got %s %s)"
-                            % (what, frames.dtype, shape))
-    lead = 0 if frames.dim() == (3 if colour else 2) else 1
-    H, W = int(shape[lead]), int(shape[lead + 1])
-    if not (1 <= H <= 65535 and 1 <= W <= 65535):
-        raise ValueError("%s: H and W must be in [1, 65535] (got %dx%d)" % (what, H, W))
-    if not frames.is_cuda:
-        raise _lib.CsmError("%s: frames must be a device tensor; libcsm355 has no CPU path" % what)
-    im = frames.contiguous()
-    im = im.view(torch.uint8) if mask else im
-    return (im if lead else im.unsqueeze(0)), colour, mask
-
-
 def gif_quantize(frames, palette=None, dither='ordered', bgr=True):
     """Frames to palette indices (contract DESIGN.md §4.10): returns (indices, palette), indices device uint8 [n,H,W], palette host
     uint8 [256,3] in R, G, B order.  frames: device uint8 [n,H,W,3] or [H,W,3] (B, G, R in memory unless bgr=False), uint8 [n,H,W] or
@@ -1501,7 +1443,7 @@ def gif_quantize(frames, palette=None, dither='ordered', bgr=True):
         raise ValueError("gif_quantize: dither must be 'ordered' or 'none' (got %r)" % (dither,))
     if palette is not None:
         palette = gifcode.check_palette(palette)
-    im, colour, mask = _gif_frames(frames, "gif_quantize")
+    im, colour, mask = _image_batch(frames, "gif_quantize", lambda H, W, C: _check_sides("gif_quantize", H, W))
     if not colour:
         return (im * 255 if mask else im), gifcode.grey_palette()
     n, H, W = (int(v) for v in im.shape[:3])
@@ -1529,8 +1471,7 @@ def gif_streams(indices):
     if indices.dtype != torch.uint8 or indices.dim() not in (2, 3):
         raise _lib.CsmError("gif_streams: uint8 [n,H,W] or [H,W] indices expected (got %s %s)" % (indices.dtype, tuple(indices.shape)))
     H, W = (int(v) for v in indices.shape[-2:])
-    if not (1 <= H <= 65535 and 1 <= W <= 65535):
-        raise ValueError("gif_streams: H and W must be in [1, 65535] (got %dx%d)" % (H, W))
+    _check_sides("gif_streams", H, W)
     if not indices.is_cuda:
         raise _lib.CsmError("gif_streams: indices must be a device tensor; libcsm355 has no CPU path")
     im = indices.contiguous()                                   # named: alive until the kernels that read it are enqueued
