@@ -65,6 +65,7 @@ def load():
         _lib.csm_leres_post_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_webpll_plan.restype = ctypes.c_size_t
         _lib.csm_webp_decode_scratch_bytes.restype = ctypes.c_size_t
+        _lib.csm_webp_lossy_decode_scratch_bytes.restype = ctypes.c_size_t
         if os.environ.get("CSM_TUNER_OPTIONS"):          # measurement aid (A/B of launch forms, include/csm355.h csm_debug_conv_tuner_options); speed only
             # the value is the WHOLE bitmask (default 1 = mixed-tile launches on; bit 1 = N-grouped tile order off): "2" also clears bit 0
             import sys

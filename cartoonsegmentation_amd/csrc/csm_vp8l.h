@@ -406,6 +406,64 @@ CSM_VP8L_FN void decode_file(State &S, const Bufs &B, const uint8_t *in, uint32_
     R.err = S.err;
 }
 
+// The same walk for a stream that begins behind the 5-byte header: the alpha plane of a lossy file (an ALPH chunk of compression 1;
+// csm_vp8dec.h), whose size is the frame's and whose values are the green channel.
+CSM_VP8L_FN void decode_headerless(State &S, const Bufs &B, const uint8_t *in, uint32_t in_len, uint32_t W, uint32_t H, Result &R) {
+    start(S, in, in_len);
+    R.ntrans = 0; R.pal_n = 0; R.main_xs = (int32_t)W; R.ngroups = 0; R.meta_bits = 0; R.cache_bits = 0; R.bytes_used = 0; R.has_alpha = 0;
+    uint32_t xs = W, seen = 0;
+    while (!S.err && take(S, 1)) {
+        if (past_end(S)) { S.err |= kErrEnd; break; }
+        const int type = (int)take(S, 2);
+        if (seen >> type & 1u) { S.err |= kErrTransform; break; }
+        seen |= 1u << type;
+        const int t = R.ntrans++;
+        R.type[t] = type; R.xs[t] = (int32_t)xs; R.bits[t] = 0;
+        if (type == kPredictor || type == kCrossColour) {
+            const int bits = (int)take(S, 3) + 2;
+            R.bits[t] = bits;
+            decode_sub(S, B, type == kPredictor ? B.pred : B.colour, subsample(xs, bits), subsample(H, bits));
+        } else if (type == kPalette) {
+            const int n = (int)take(S, 8) + 1;
+            const int bits = n > 16 ? 0 : n > 4 ? 1 : n > 2 ? 2 : 3;
+            R.bits[t] = bits; R.pal_n = n;
+            decode_sub(S, B, B.palette, (uint32_t)n, 1);
+            if (S.err) break;
+            for (int i = 1; i < n; ++i) B.palette[i] = add_bytes(B.palette[i], B.palette[i - 1]);
+            for (int i = n; i < 256; ++i) B.palette[i] = 0;
+            xs = subsample(xs, bits);
+        }
+    }
+    int cache_bits = 0;
+    const uint32_t *meta = nullptr;
+    uint32_t meta_w = 0, ngroups = 1;
+    int meta_bits = 0;
+    if (!S.err && read_cache_bits(S, cache_bits)) {
+        if (take(S, 1)) {
+            meta_bits = (int)take(S, 3) + 2;
+            meta_w = subsample(xs, meta_bits);
+            const uint32_t meta_h = subsample(H, meta_bits);
+            decode_sub(S, B, B.meta, meta_w, meta_h);
+            if (!S.err) {
+                uint32_t top = 0;
+                for (uint32_t i = 0; i < meta_w * meta_h; ++i) {
+                    const uint32_t v = (B.meta[i] >> 8) & 0xffffu;
+                    top = v > top ? v : top;
+                }
+                ngroups = top + 1;
+                meta = B.meta;
+            }
+        }
+        R.ngroups = ngroups; R.meta_bits = (uint32_t)meta_bits; R.cache_bits = (uint32_t)cache_bits;
+        if (!S.err && ngroups > B.group_cap) S.err |= kErrCap;
+        for (uint32_t k = 0; k < ngroups && !S.err; ++k) read_group(S, B.groups[k], cache_bits);
+        if (!S.err) decode_pixels(S, B, B.argb, xs, H, cache_bits, meta, meta_bits, meta_w);
+    }
+    R.main_xs = (int32_t)xs;
+    R.bytes_used = (uint32_t)((S.pos + 7) >> 3);
+    R.err = S.err;
+}
+
 // ---- the inverse transforms, per pixel ------------------------------------------------------------------------------------------
 CSM_VP8L_FN uint32_t avg2(uint32_t a, uint32_t b) { return (((a ^ b) & 0xfefefefeu) >> 1) + (a & b); }
 

@@ -17,8 +17,12 @@
 //
 // No kernel waits on another workgroup and there is no spin loop on memory.  Every read and store is bounded by sizes from the
 // descriptor, whatever the data: a corrupt stream raises bits of the file's error word and leaves the file's pixels undefined.
+//
+// The same kernels decode the alpha planes of lossy files (webplossy.hip through csm_webpdec.h): such a "file" is
+// a stream without the 5-byte header, and its store writes the green channel as one byte per pixel.
 #include "csm_common.h"
 #include "csm_vp8l.h"
+#include "csm_webpdec.h"
 #include <algorithm>
 #include <vector>
 
@@ -34,6 +38,7 @@ constexpr int kMaxSide = 16384;
 struct WFile {
     // from the caller's descriptor
     int H, W, alpha, channels;
+    int plane;                               // the lossy decoder's alpha plane: a stream without the 5-byte header, stored as its green bytes
     int in_off, in_len;
     int64_t out_off;
     // derived
@@ -48,7 +53,7 @@ struct Plan {
 };
 
 // false: the descriptors are invalid (the error is set)
-bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes, bool check_ranges, Plan &p) {
+bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes, bool check_ranges, bool planes, Plan &p) {
     if (!desc || n < 1 || n > 65535) { csm::set_error("invalid argument: 1 <= n <= 65535 descriptors"); return false; }
     p.files.resize(n);
     int64_t o = 0;
@@ -57,10 +62,11 @@ bool make_plan(const int32_t *desc, int n, int64_t blob_bytes, int64_t out_bytes
     for (int i = 0; i < n; ++i) {
         const int32_t *d = desc + (int64_t)i * kDescWords;
         WFile &f = p.files[i];
-        f.H = d[0]; f.W = d[1]; f.alpha = d[2]; f.channels = d[3]; f.in_off = d[4]; f.in_len = d[5];
+        f.H = d[0]; f.W = d[1]; f.alpha = d[2]; f.channels = d[3]; f.in_off = d[4]; f.in_len = d[5]; f.plane = d[6];
         f.out_off = (int64_t)d[7] | ((int64_t)d[8] << 31);
-        bool ok = f.H >= 1 && f.W >= 1 && f.H <= kMaxSide && f.W <= kMaxSide && (f.alpha == 0 || f.alpha == 1) && (f.channels == 3 || f.channels == 4);
-        ok = ok && f.in_off >= 0 && (f.in_off & 15) == 0 && f.in_len >= 5 && d[7] >= 0 && d[8] >= 0 && (f.out_off & 3) == 0;
+        bool ok = f.H >= 1 && f.W >= 1 && f.H <= kMaxSide && f.W <= kMaxSide && (f.alpha == 0 || f.alpha == 1);
+        ok = ok && (planes ? f.plane == 1 && f.channels == 1 : f.plane == 0 && (f.channels == 3 || f.channels == 4));
+        ok = ok && f.in_off >= 0 && (f.in_off & 15) == 0 && f.in_len >= (planes ? 1 : 5) && d[7] >= 0 && d[8] >= 0 && (f.out_off & 3) == 0;
         if (ok && check_ranges)
             ok = (int64_t)f.in_off + f.in_len <= blob_bytes && f.out_off + (int64_t)f.H * f.W * f.channels <= out_bytes;
         if (!ok) { csm::set_error("invalid argument: descriptor %d of the WebP decode", i); return false; }
@@ -97,7 +103,9 @@ __global__ __launch_bounds__(64) void k_wd_walk(const uint8_t *__restrict__ blob
     B.groups = (vp::Group *)(scratch + f.group_off);
     B.sub_cap = f.sub_cap;
     B.group_cap = f.group_cap;
-    vp::decode_file(S, B, blob + f.in_off, (uint32_t)f.in_len, (uint32_t)f.W, (uint32_t)f.H, *(vp::Result *)(scratch + f.res_off));
+    vp::Result &R = *(vp::Result *)(scratch + f.res_off);
+    if (f.plane) vp::decode_headerless(S, B, blob + f.in_off, (uint32_t)f.in_len, (uint32_t)f.W, (uint32_t)f.H, R);
+    else vp::decode_file(S, B, blob + f.in_off, (uint32_t)f.in_len, (uint32_t)f.W, (uint32_t)f.H, R);
 }
 
 // ---- the inverse transforms -----------------------------------------------------------------------------------------------------
@@ -174,6 +182,7 @@ __global__ __launch_bounds__(kLanes) void k_wd_store(const WFile *__restrict__ f
     const uint32_t p = (uint32_t)blockIdx.x * kLanes + threadIdx.x;
     if (p >= (uint32_t)f.W * (uint32_t)f.H) return;
     const uint32_t v = ((const uint32_t *)(scratch + f.argb_off[R.ntrans & 1]))[p];
+    if (f.plane) { out[f.out_off + p] = (uint8_t)(v >> 8); return; }
     uint8_t *q = out + f.out_off + (int64_t)p * f.channels;
     q[0] = (uint8_t)v; q[1] = (uint8_t)(v >> 8); q[2] = (uint8_t)(v >> 16);
     if (f.channels == 4) q[3] = R.has_alpha ? (uint8_t)(v >> 24) : 255;
@@ -185,18 +194,20 @@ extern "C" int csm_webp_decode_desc_words(void) { return kDescWords; }
 
 extern "C" size_t csm_webp_decode_scratch_bytes(const int32_t *desc_host, int n) {
     Plan p;
-    if (!make_plan(desc_host, n, 0, 0, false, p)) return 0;
+    if (!make_plan(desc_host, n, 0, 0, false, false, p)) return 0;
     return (size_t)p.total;
 }
 
-extern "C" int csm_webp_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
-                               void *scratch, int *info_host, void *stream) {
-    if (n == 0) return CSM_OK;
-    CSM_REQUIRE(blob && desc_host && out && scratch && blob_bytes > 0 && out_bytes > 0);
-    CSM_REQUIRE(((uintptr_t)blob & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)scratch & 15) == 0);
+size_t csm::vp8l_scratch_bytes(const int32_t *desc_host, int n, bool planes) {
     Plan p;
-    if (!make_plan(desc_host, n, blob_bytes, out_bytes, true, p)) return CSM_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
+    if (!make_plan(desc_host, n, 0, 0, false, planes, p)) return 0;
+    return (size_t)p.total;
+}
+
+int csm::vp8l_launch(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes, void *scratch,
+                     bool planes, hipStream_t st) {
+    Plan p;
+    if (!make_plan(desc_host, n, blob_bytes, out_bytes, true, planes, p)) return CSM_ERR_ARG;
     char *S = (char *)scratch;
     WFile *files = (WFile *)(S + p.o_files);
     // p.files is pageable host memory: the runtime stages such a copy before hipMemcpyAsync returns
@@ -211,17 +222,36 @@ extern "C" int csm_webp_decode(const uint8_t *blob, int64_t blob_bytes, const in
         rc = csm::check_launch("k_wd_predict"); if (rc) return rc;
     }
     k_wd_store<<<pixel_grid, kLanes, 0, st>>>(files, S, out);
-    rc = csm::check_launch("k_wd_store"); if (rc) return rc;
+    return csm::check_launch("k_wd_store");
+}
+
+int csm::vp8l_errors(const void *scratch, int n, uint32_t *err_host, hipStream_t st) {
     std::vector<vp::Result> res(n);
-    CSM_HIP(hipMemcpyAsync(res.data(), S + p.o_res, (size_t)n * sizeof(vp::Result), hipMemcpyDeviceToHost, st));
+    CSM_HIP(hipMemcpyAsync(res.data(), (const char *)scratch + csm::align16((int64_t)n * sizeof(WFile)), (size_t)n * sizeof(vp::Result),
+                           hipMemcpyDeviceToHost, st));
     CSM_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) err_host[i] = res[i].err;
+    return CSM_OK;
+}
+
+extern "C" int csm_webp_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
+                               void *scratch, int *info_host, void *stream) {
+    if (n == 0) return CSM_OK;
+    CSM_REQUIRE(blob && desc_host && out && scratch && blob_bytes > 0 && out_bytes > 0);
+    CSM_REQUIRE(((uintptr_t)blob & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)scratch & 15) == 0);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = csm::vp8l_launch(blob, blob_bytes, desc_host, n, out, out_bytes, scratch, false, st);
+    if (rc) return rc;
+    std::vector<uint32_t> err(n);
+    rc = csm::vp8l_errors(scratch, n, err.data(), st);
+    if (rc) return rc;
     int bad = -1;
     for (int i = 0; i < n; ++i) {
-        if (info_host) info_host[i] = (int)res[i].err;
-        if ((res[i].err & ~(uint32_t)vp::kErrCap) && bad < 0) bad = i;
+        if (info_host) info_host[i] = (int)err[i];
+        if ((err[i] & ~(uint32_t)vp::kErrCap) && bad < 0) bad = i;
     }
     if (bad >= 0) {
-        csm::set_error("webp decode: file %d of the call has corrupt data (error word 0x%x: see csm_vp8l.h)", bad, res[bad].err);
+        csm::set_error("webp decode: file %d of the call has corrupt data (error word 0x%x: see csm_vp8l.h)", bad, err[bad]);
         return CSM_ERR_DATA;
     }
     return CSM_OK;

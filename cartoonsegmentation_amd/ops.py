@@ -975,55 +975,87 @@ def png_decode(files, device=None, stats=None, _infos=None):
     return out[0] if single else out
 
 
-# ---- lossless WebP files to device frames (csrc/webpdec.hip + webpread.py; utils.io_utils.imread_device) -------------------------
+# ---- WebP files to device frames (csrc/webpdec.hip, csrc/webplossy.hip + webpread.py; utils.io_utils.imread_device) ------------
 WEBP_DECODE_SCRATCH_BYTES = 64 << 20   # files are decoded in chunks whose scratch stays below this (one file is always taken)
+WEBP_LOSSY_DECODE_SCRATCH_BYTES = 64 << 20   # the same for the lossy files of a call, which go to native calls of their own
 
 
-def webp_decode(files, device=None, alpha=False, stats=None, _infos=None):
-    """Lossless WebP files (VP8L; contract DESIGN.md §4.15) to device uint8 tensors: [H,W,3] in B, G, R order, equal to
-    utils.io_utils.imread on every byte, or with alpha=True [H,W,4] in B, G, R, A order, equal to PIL's convert('RGBA') (a file whose
-    header says "no alpha" gets A = 255).  `files` is one `bytes` (one tensor is returned) or a list of `bytes` (a list is
-    returned); sizes and features may differ within a call.  The host walks the RIFF container (webpread.probe; a file the decoder
-    does not take -- lossy, animated, rotated -- raises webpread.Unsupported) and uploads only the VP8L chunks' payloads; the
-    entropy decode, the inverse transforms and the colour store run on the device (csm_webp_decode) in chunks of files whose
-    scratch stays below WEBP_DECODE_SCRATCH_BYTES.  A corrupt stream raises CsmError.  A valid file with more prefix-code groups
-    than the cap (webpread.GROUP_CAP, or one per 4 x 4 pixels in a smaller image) raises webpread.Unsupported after the decode,
-    with the indices of such files in its `files` attribute.  The tensors of a chunk are views of one allocation.  `stats` (a
-    dict) receives 'chunks': the number of files of every native call."""
+def _webp_layout(part, out_off, channels, words, lossy):
+    """_decode_groups' layout of WebP files: every VP8L / VP8 payload, and behind them every ALPH chunk's bytes behind its first,
+    on 16-byte boundaries of the blob"""
+    from . import webpread
+    blob_off, alph_off, o = [], [], 0
+    for _, info in part:
+        blob_off.append(o)
+        o += (info['payload'][1] - info['payload'][0] + 15) & ~15
+    for _, info in part:
+        alph_off.append(o)
+        if lossy and info['alph']:
+            o += (info['alph'][1] - info['alph'][0] - 1 + 15) & ~15
+    desc = _np.zeros((len(part), words), _np.int32)
+    for j, (d, info) in enumerate(part):
+        if lossy:
+            head = d[info['alph'][0]] if info['alph'] else 0
+            desc[j] = webpread.lossy_descriptor(info, blob_off[j], out_off[j], channels, head, alph_off[j])
+        else:
+            desc[j] = webpread.descriptor(info, blob_off[j], out_off[j], channels)
+
+    def fill(blob_h):
+        for j, (d, info) in enumerate(part):
+            p = webpread.payload(d, info)
+            blob_h[blob_off[j]:blob_off[j] + p.size] = p
+            if lossy and info['alph']:
+                s, e = info['alph']
+                blob_h[alph_off[j]:alph_off[j] + e - s - 1] = _np.frombuffer(d, _np.uint8, e - s - 1, s + 1)
+    return max(o, 16), (desc,), fill
+
+
+def webp_decode(files, device=None, alpha=False, stats=None, _infos=None, lossy=False):
+    """WebP files to device uint8 tensors: [H,W,3] in B, G, R order, equal to utils.io_utils.imread on every byte, or with
+    alpha=True [H,W,4] in B, G, R, A order, equal to PIL's convert('RGBA') (a file without alpha gets A = 255).  `files` is one
+    `bytes` (one tensor is returned) or a list of `bytes` (a list is returned); sizes and features may differ within a call.
+    Lossless files (VP8L; contract DESIGN.md §4.15) are always taken; lossy=True also takes lossy files (a VP8 key frame with or
+    without an ALPH chunk; §4.16), mixed with lossless ones in any order: each kind goes to its own native calls (csm_webp_decode,
+    csm_webp_lossy_decode) in chunks of files whose scratch stays below WEBP_DECODE_SCRATCH_BYTES and
+    WEBP_LOSSY_DECODE_SCRATCH_BYTES, and the results come back in input order.  The host walks the RIFF container
+    (webpread.probe; a file the decoders do not take -- animated, rotated, without lossy=True lossy -- raises
+    webpread.Unsupported) and uploads only the chunks' payloads; entropy decoding, reconstruction and the colour store run on the
+    device.  A corrupt stream raises CsmError.  A valid file with more prefix-code groups than the cap (webpread.GROUP_CAP, or
+    one per 4 x 4 pixels in a smaller image; for a lossy file: in its alpha plane's stream) raises webpread.Unsupported after
+    the decode, with the indices of such files in its `files` attribute.  The tensors of a chunk are views of one allocation.
+    `stats` (a dict) receives 'chunks': the number of files of every native call of the lossless decoder, and with lossy=True
+    'chunks_lossy': the same for the lossy one."""
     from . import webpread
     single, datas = _byte_files(files, "webp_decode")
-    infos = _infos if _infos is not None else [webpread.probe(d) for d in datas]
+    infos = _infos if _infos is not None else [webpread.probe(d, lossy=True) if lossy else webpread.probe(d) for d in datas]
     dev = _gpu_device(device, "webp_decode")
     L = _lib.load()
     words = L.csm_webp_decode_desc_words()
-    assert words == webpread.DESC_WORDS
+    assert words == webpread.DESC_WORDS and L.csm_webp_lossy_decode_desc_words() == words
     channels = 4 if alpha else 3
-
-    def layout(part, out_off):
-        # the blob: every file's VP8L payload on a 16-byte boundary
-        blob_off, o = [], 0
-        for _, info in part:
-            blob_off.append(o)
-            o += (info['payload'][1] - info['payload'][0] + 15) & ~15
-        desc = _np.zeros((len(part), words), _np.int32)
-        for j, (_, info) in enumerate(part):
-            desc[j] = webpread.descriptor(info, blob_off[j], out_off[j], channels)
-
-        def fill(blob_h):
-            for j, (d, info) in enumerate(part):
-                p = webpread.payload(d, info)
-                blob_h[blob_off[j]:blob_off[j] + p.size] = p
-        return o, (desc,), fill
-
-    out, chunks, over = [], [], []
-    for i, k, info_h, tensors in _decode_groups("webp_decode", "webp_decode", datas, infos, dev, WEBP_DECODE_SCRATCH_BYTES, channels,
-                                                layout, L.csm_webp_decode_scratch_bytes, L.csm_webp_decode, info_per_file=True):
-        over += [i + j for j in range(k) if info_h[j] & webpread.ERR_CAP]
-        chunks.append(k)
-        out += tensors
+    out, over, chunks = [None] * len(datas), [], {False: [], True: []}
+    for kind in (False, True):
+        which = [i for i, info in enumerate(infos) if (info.get('kind') == 'lossy') == kind]
+        if not which:
+            continue
+        budget, scratch_fn, decode_fn, cap = ((WEBP_LOSSY_DECODE_SCRATCH_BYTES, L.csm_webp_lossy_decode_scratch_bytes,
+                                               L.csm_webp_lossy_decode, webpread.LOSSY_ERR_CAP) if kind else
+                                              (WEBP_DECODE_SCRATCH_BYTES, L.csm_webp_decode_scratch_bytes, L.csm_webp_decode,
+                                               webpread.ERR_CAP))
+        for i, k, info_h, tensors in _decode_groups("webp_decode", "webp_lossy_decode" if kind else "webp_decode",
+                                                    [datas[i] for i in which], [infos[i] for i in which], dev, budget, channels,
+                                                    lambda part, out_off: _webp_layout(part, out_off, channels, words, kind),
+                                                    scratch_fn, decode_fn, info_per_file=True):
+            over += [which[i + j] for j in range(k) if info_h[j] & cap]
+            chunks[kind].append(k)
+            for j, t in enumerate(tensors):
+                out[which[i + j]] = t
     if stats is not None:
-        stats['chunks'] = chunks
+        stats['chunks'] = chunks[False]
+        if lossy:
+            stats['chunks_lossy'] = chunks[True]
     if over:
+        over.sort()
         e = webpread.Unsupported("webp_decode: file(s) %s of the call hold more prefix-code groups than the decoder's cap (%d)"
                                  % (over, webpread.GROUP_CAP))
         e.files = tuple(over)

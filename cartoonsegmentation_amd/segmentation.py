@@ -288,7 +288,8 @@ class AnimeInsSeg:
     def _load(self, imgs):
         """the path entries of `imgs` as images: imread (host, PIL), or with device_decode imread_device_many, one call per det_batch
         chunk (baseline JPEG and 8-bit PNG files are then decoded on the device, DESIGN.md §4.8 and §4.9, and with
-        CSM_DEVICE_DECODE_WEBP=1 lossless WebP files as well, §4.15; every other file still goes through imread)"""
+        CSM_DEVICE_DECODE_WEBP=1 lossless WebP files as well, §4.15, and with CSM_DEVICE_DECODE_WEBP_LOSSY=1 beside it lossy ones,
+        §4.16; every other file still goes through imread)"""
         from utils.io_utils import imread, imread_device_many
         if not self.device_decode:
             return [imread(im) if isinstance(im, str) else im for im in imgs]

@@ -1,5 +1,6 @@
 """Motion-JPEG AVI container, animated-PNG container, animated-GIF and animated-WebP file (pure host code): the video files of the
 Ken Burns path, from frames that ops.jpeg_encode / ops.png_streams / ops.gif_streams / ops.webp_streams compressed on the device.
+read_webp reads the animated WebP files back, its frames decoded on the device.
 
 A classic RIFF AVI (AVI 1.0, no OpenDML extension, so below 2 GiB):
 
@@ -135,3 +136,22 @@ def write_webp(path, streams, width, height, fps=25, loop=0, order=None):
     with open(path, 'wb') as f:
         f.write(data)
     return len(data)
+
+
+def read_webp(path_or_bytes, device=None):
+    """Read an animated WebP as write_webp writes it (every frame at offset 0, covering the canvas, one bare VP8 key frame without
+    alpha): (uint8 device tensor [n,H,W,3] in B, G, R order, frames in file order; the n durations in ms).  All frames are decoded
+    in one ops.webp_decode call (the lossy decoder, DESIGN.md §4.16: equal to what PIL shows after seek(i) on every byte); only the
+    VP8 chunks' bytes are uploaded.  Any other animation (sub-rectangles, alpha, lossless frames) raises webpread.Unsupported."""
+    import torch
+    from . import ops, webpread
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, 'rb') as f:
+            data = f.read()
+    width, height, frames, durations = webpread.animation_frames(data)
+    infos = [{'width': width, 'height': height, 'alpha': False, 'payload': fr, 'alph': None, 'extended': False, 'orientation': None,
+              'kind': 'lossy'} for fr in frames]
+    tensors = ops.webp_decode([data] * len(frames), device, _infos=infos, lossy=True)
+    return torch.stack(tensors), durations

@@ -679,6 +679,36 @@ int csm_webp_decode_desc_words(void);
 int csm_webp_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
                     void *scratch, int *info_host, void *stream);
 
+/* Lossy WebP files (a VP8 key frame, with or without an ALPH chunk) to uint8 B, G, R or B, G, R, A pixels (webplossy.hip; contract
+ * DESIGN.md §4.16, restated in tests/webplossy_restatement.py: the result equals what libwebp decodes on every byte).  The host
+ * parses the RIFF container (cartoonsegmentation_amd/webpread.py) and hands over one blob of device bytes and one descriptor per
+ * file; files of different sizes and features share a call.  Everything a key frame can hold is taken: segmentation with map and
+ * absolute or delta values, both loop filters with sharpness and filter deltas, 1 .. 8 token partitions, all six quantiser indices,
+ * coefficient-probability updates, skipping on or off, the four whole-block and the ten sub-block modes.  An ALPH chunk may be raw
+ * or a VP8L stream (then the lossless decoder's limit of prefix-code groups applies to it), with filter 0 .. 3.
+ * desc_host: host int32 [n][csm_webp_lossy_decode_desc_words() = 12]: [0] H, [1] W (each 1 .. 16383, as the frame header says),
+ *   [2] 1 if the file has an ALPH chunk, [3] the output channels (3: B, G, R; 4: B, G, R, A), [4] [5] offset (a multiple of 16) and
+ *   length of the VP8 chunk's payload in the blob, [6] the first byte of the ALPH chunk (compression, filter, pre-processing),
+ *   [7] [8] the byte offset of the file's pixels in out (low 31 bits, the bits above; a multiple of 4), [9] [10] offset (a multiple
+ *   of 16) and length of the ALPH chunk's bytes behind its first, [11] 0.
+ * out: u8, file i at its offset as [H][W][channels]; A is 255 where the file has no ALPH chunk.  With 3 channels the ALPH chunk is
+ *   not looked at.  blob, out and scratch are 16-byte aligned.
+ * scratch: csm_webp_lossy_decode_scratch_bytes(desc_host, n) device bytes (0 for invalid descriptors), a function of the
+ *   descriptors alone: per macroblock 824 B (a 24-byte record, 25 x 16 int16 coefficients) and 384 B of planes, per macroblock
+ *   column 13 B of contexts, with 4 channels and an ALPH chunk 1 B per pixel, and for ALPH chunks of compression 1 what
+ *   csm_webp_decode takes for a file of that size.
+ * csm_webp_lossy_decode: info_host (may be NULL) receives n words, the error word of every file (bits as in csrc/csm_vp8dec.h; from
+ *   bit 8 up the error word of the alpha plane's VP8L stream, csrc/csm_vp8l.h).  The call SYNCHRONISES the stream once, at the end.
+ *   Returns CSM_ERR_DATA for a corrupt file (a frame tag, start code or size that contradicts the descriptor, partition sizes that
+ *   run past the chunk, a partition that ends early, a bad ALPH chunk).  An alpha stream with more groups than the cap is not
+ *   corrupt: the call returns CSM_OK (unless another file is corrupt), bit 32 << 8 of that file's word is set and its alpha is not
+ *   written.  Whatever the data, no read or store leaves the file's own ranges.  No kernel waits on another workgroup; the output
+ *   is deterministic. */
+size_t csm_webp_lossy_decode_scratch_bytes(const int32_t *desc_host, int n);
+int csm_webp_lossy_decode_desc_words(void);
+int csm_webp_lossy_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
+                          void *scratch, int *info_host, void *stream);
+
 /* The device half of a GIF file (gif.hip; contract DESIGN.md §4.10, restated in tests/gif_restatement.py, byte-identical): one
  * 256-colour palette per clip and the LZW stream (minimum code size 8) of every frame.  1 <= H, W <= 65535.
  * csm_gif_histogram: frames u8 [pixels][3], contiguous; flags bit 0 = the channels are B, G, R in memory.  table device uint32

@@ -30,7 +30,7 @@ def imread(path):
         return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
 
 
-def imread_device_many(paths, device=None, stats=None, progressive=None, webp=None):
+def imread_device_many(paths, device=None, stats=None, progressive=None, webp=None, webp_lossy=None):
     """imread for a list of paths with the pixels on the device: a list of uint8 BGR [H,W,3] tensors.  A .jpg / .jpeg file that the
     device decoder takes (cartoonsegmentation_amd.jpegcode.probe: baseline, Huffman, grey or Y Cb Cr at 4:4:4 / 4:2:2 / 4:2:0) and
     whose EXIF orientation is 1 or absent is decoded on the MI355X by ops.jpeg_decode, all such files in one call: only the file's
@@ -50,11 +50,20 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
     that cartoonsegmentation_amd.webpread.probe accepts (lossless, not animated, orientation 1 or absent) to the device
     (ops.webp_decode, DESIGN.md §4.15: equal to imread on every byte), all such files in one call.  Lossy and animated files, and
     files with more prefix-code groups than the decoder's cap, stay with imread.  `stats` then also receives 'webp', the indices of
-    the files decoded on the device.  With the option off nothing changes: a .webp path goes through imread."""
+    the files decoded on the device.  With the option off nothing changes: a .webp path goes through imread.
+
+    webp_lossy=True (None reads the environment variable CSM_DEVICE_DECODE_WEBP_LOSSY, '1' = on; the default is off) has an effect
+    only together with the webp option: the lossy .webp files that webpread.probe(data, lossy=True) accepts (a VP8 key frame with or
+    without an ALPH chunk, not animated, orientation 1 or absent) then go to the device as well (equal to imread on
+    every byte), in the same ops.webp_decode call as the lossless ones.  `stats['webp']` lists them with the lossless files, and
+    `stats` also receives 'webp_lossy', the indices of the lossy ones.  With the option off, routing and `stats` are unchanged."""
     import torch
     from cartoonsegmentation_amd import jpegcode, ops, pngread, webpread
     if webp is None:
         webp = os.environ.get('CSM_DEVICE_DECODE_WEBP', '0') == '1'
+    if webp_lossy is None:
+        webp_lossy = os.environ.get('CSM_DEVICE_DECODE_WEBP_LOSSY', '0') == '1'
+    webp_lossy = bool(webp and webp_lossy)
     if progressive is None:
         progressive = os.environ.get('CSM_DEVICE_DECODE_PROGRESSIVE', '0') == '1'
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -89,7 +98,7 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
             with open(path, 'rb') as f:
                 data = f.read()
             try:
-                info = webpread.probe(data)
+                info = webpread.probe(data, lossy=True) if webp_lossy else webpread.probe(data)
             except webpread.Unsupported:
                 info = None
             if info is not None:
@@ -105,7 +114,7 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
             out[i] = t
     while wdatas:
         try:
-            for i, t in zip(widx, ops.webp_decode(wdatas, dev, _infos=winfos)):
+            for i, t in zip(widx, ops.webp_decode(wdatas, dev, _infos=winfos, lossy=webp_lossy)):
                 out[i] = t
             break
         except webpread.Unsupported as e:                          # files over the group cap: they go through imread, the rest again
@@ -120,14 +129,16 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
         stats.update(jpeg=idx, png=pidx, host=host)
         if webp:
             stats['webp'] = widx
+        if webp_lossy:
+            stats['webp_lossy'] = [i for i, info in zip(widx, winfos) if info['kind'] == 'lossy']
         if progressive:
             stats['jpeg_progressive'] = [i for i, info in zip(idx, infos) if info['progressive']]
     return out
 
 
-def imread_device(path, device=None, progressive=None, webp=None):
+def imread_device(path, device=None, progressive=None, webp=None, webp_lossy=None):
     """imread with the pixels on the device: see imread_device_many"""
-    return imread_device_many([path], device, progressive=progressive, webp=webp)[0]
+    return imread_device_many([path], device, progressive=progressive, webp=webp, webp_lossy=webp_lossy)[0]
 
 
 def imwrite(img, file_path, auto_mkdir=True):
