@@ -1,5 +1,7 @@
 // csm_jpeg.h -- what the JPEG decoders of jpegdec.hip (baseline) and jpegprog.hip (progressive, §4.11) share: the
-// file descriptor and the scratch plan, the bit reader, the Huffman tables in LDS, and the kernels from the coefficient store to the
+// file descriptor and the scratch plan, the bit reader, the Huffman tables in LDS, the subsequence machine of the entropy decode
+// (k_js_sync_local, k_js_sync_global, k_js_scan, k_js_write and the host loop that runs them, templates over a codec policy that
+// each file instantiates with its own), the segmented scan of the DC prediction, and the kernels from the coefficient store to the
 // pixels (k_jd_idct, k_jd_colour).  Included by those two files only; everything is local to the including file.
 #pragma once
 #include "csm_common.h"
@@ -164,20 +166,204 @@ struct Reader {
     }
 };
 
-struct Tables {                 // of one file, in LDS: jpegcode.file_tables without the quantisation tables
-    uint32_t w[kHuffSlots * kTableBytes / 4];
+template <int N> struct HuffTables {            // N decode tables (jpegcode.TABLE_BYTES each) in LDS
+    uint32_t w[N * kTableBytes / 4];
     __device__ __forceinline__ const uint16_t *lut(int s) const { return (const uint16_t *)((const uint8_t *)w + s * kTableBytes); }
     __device__ __forceinline__ const int *maxcode(int s) const { return (const int *)((const uint8_t *)w + s * kTableBytes + 512); }
     __device__ __forceinline__ const int *valoff(int s) const { return (const int *)((const uint8_t *)w + s * kTableBytes + 584); }
     __device__ __forceinline__ const uint8_t *vals(int s) const { return (const uint8_t *)w + s * kTableBytes + 656; }
 };
 
-__device__ __forceinline__ void load_tables(Tables &T, const uint8_t *blob, const JFile &f) {
-    const uint32_t *src = (const uint32_t *)(blob + f.tab_off);
-    for (int i = threadIdx.x; i < kHuffSlots * kTableBytes / 4; i += blockDim.x) T.w[i] = src[i];
+// the first n (<= N) tables from src (4-byte aligned), by the whole workgroup
+template <int N> __device__ __forceinline__ void load_tables(HuffTables<N> &T, const uint8_t *src, int n) {
+    for (int i = threadIdx.x; i < n * (kTableBytes / 4); i += blockDim.x) T.w[i] = ((const uint32_t *)src)[i];
 }
 
-// ---- output positions -------------------------------------------------------------------------------------------------------
+// the code at the top of v (the next 32 bits) in table `slot`: false for an invalid code
+template <int N> __device__ __forceinline__ bool huff_decode(const HuffTables<N> &T, int slot, uint32_t v, int &ln, int &sym) {
+    const uint32_t e = T.lut(slot)[v >> 24];
+    if (e) { ln = (int)(e >> 8); sym = (int)(e & 255u); return true; }
+    const int *mc = T.maxcode(slot);
+    const int code16 = (int)(v >> 16);
+    int c = 0;
+    for (ln = 9; ln <= 16; ++ln) { c = code16 >> (16 - ln); if (c <= mc[ln]) break; }
+    if (ln > 16) return false;
+    sym = T.vals(slot)[(T.valoff(slot)[ln] + c) & 255];
+    return true;
+}
+
+// ---- the subsequence machine --------------------------------------------------------------------------------------------------
+// The self-synchronising decode of Weissenberger and Schmidt (ICPP 2018) over work items (a baseline file, a progressive first scan)
+// whose entropy bytes are cut into subsequences of kSubseq bytes, a lane to each, kLanes of them to a workgroup.  A lane's state is
+// (bit position, b, z); it counts the coefficient slots and the restart markers it passes.  What a codec adds is a policy P:
+//
+//   using Tables = HuffTables<n>;  struct Args { ... };             what the kernels are handed to find the work items
+//   P(const Args &, int item)                                       work item `item` of the launch
+//   seq()                                                           the descriptor that holds ent_off, ent_len, sub0, nsub, nwg
+//   load(T, blob)                                                   the item's tables, by the whole workgroup
+//   table(b, z)                                                     table slot of the next symbol
+//   symbol(sym, z, y)                                               fills y for Huffman symbol `sym`; false: invalid in this state
+//   advance(y, bits, b, z)                                          the slots the symbol takes (bits: its y.extra bits); moves (b, z) on
+//   clamp(b, z)                                                     brings a state read from memory into range
+//   store(coef, at, val)                                            coefficient `val` at slot `at` of the item (bounds checked)
+//   interval_slots(), total_slots(), err_index(item)                slots of a restart interval, of the item; its word of err
+struct Symbol {
+    int adv;             // slots it takes where that is known before its extra bits are read
+    int size;            // bits of its coefficient's value; 0: no coefficient
+    int extra;           // raw bits behind the code
+};
+
+struct Sink {            // what the coefficient stores of the write pass need
+    int16_t *coef;
+    int64_t slot;        // slot of the current state
+    int64_t per_marker;  // slots of a restart interval
+    int marks_before;
+};
+
+__device__ __forceinline__ uint64_t pack_state(uint32_t p, int b, int z) { return ((uint64_t)p << 16) | ((uint64_t)b << 8) | (uint64_t)z; }
+
+// Decodes symbols from (rd, b, z) while the next symbol begins before bit `limit` of the item's entropy bytes.  Returns the packed
+// end state, kDead after an invalid code.  n_slots / n_mark count the coefficient slots and the restart markers passed.
+template <bool EMIT, class P>
+__device__ uint64_t subseq_run(const P &w, const typename P::Tables &T, Reader &rd, int &b, int &z, uint32_t limit, int &n_slots,
+                               int &n_mark, Sink &sink) {
+    for (;;) {
+        rd.refill();
+        bool marker = rd.at_marker();
+        Symbol y{};
+        int total = 0;
+        uint32_t v = 0;
+        if (!marker) {
+            if (rd.bitpos() >= limit) return pack_state(rd.bitpos(), b, z);
+            v = (uint32_t)(rd.win >> 32);
+            int ln, sym;
+            if (!huff_decode(T, w.table(b, z), v, ln, sym) || !w.symbol(sym, z, y)) return kDead;
+            total = ln + y.extra;                // at most 16 + 15 bits
+            marker = total > rd.nb;              // the symbol runs into a marker or the end: not a symbol
+        }
+        if (marker) {
+            if (rd.stop != 1) { b = 0; z = 0; return pack_state((uint32_t)w.seq().ent_len * 8u, 0, 0); }
+            rd.cross();
+            b = 0; z = 0;
+            ++n_mark;
+            if constexpr (EMIT) sink.slot = (int64_t)(sink.marks_before + n_mark) * sink.per_marker;
+            continue;
+        }
+        const int bits = y.extra ? (int)((v >> (32 - total)) & ((1u << y.extra) - 1u)) : 0;
+        const int adv = w.advance(y, bits, b, z);
+        if constexpr (EMIT) {
+            if (y.size) {
+                int val = bits;
+                if (val < (1 << (y.size - 1))) val -= (1 << y.size) - 1;
+                w.store(sink.coef, sink.slot + adv - 1, val);
+            }
+            sink.slot += adv;
+        }
+        rd.skip(total);
+        n_slots += adv;
+    }
+}
+
+// a reader at the packed state st (not kDead) of the item
+template <class P> __device__ __forceinline__ void open_at(const P &w, Reader &rd, const uint8_t *ent, uint64_t st, int &b, int &z) {
+    const uint32_t p = (uint32_t)(st >> 16);
+    b = (int)((st >> 8) & 255u); z = (int)(st & 255u);
+    w.clamp(b, z);
+    rd.open(ent, w.seq().ent_len, (int)min(p >> 3, (uint32_t)w.seq().ent_len));
+    rd.refill();
+    const int off = (int)(p & 7u);
+    if (off < rd.nb) rd.skip(off);
+}
+
+// grid (workgroups of the largest item, items); lane = one subsequence.  Every lane decodes its own subsequence from a cold state,
+// then goes on into its successors from its own end state, through LDS, until its end state equals the one recorded there or the
+// workgroup ends.
+template <class P>
+__global__ __launch_bounds__(kLanes) void k_js_sync_local(const uint8_t *__restrict__ blob, const typename P::Args a,
+                                                           uint64_t *__restrict__ state, int *__restrict__ cnt_n, int *__restrict__ cnt_r) {
+    __shared__ typename P::Tables T;
+    __shared__ uint64_t sState[kLanes];
+    __shared__ int sN[kLanes], sR[kLanes];
+    const P w(a, blockIdx.y);
+    const auto &q = w.seq();
+    if ((int)blockIdx.x >= q.nwg) return;
+    const int t = threadIdx.x, j = blockIdx.x * kLanes + t;
+    const bool valid = j < q.nsub;
+    const uint8_t *ent = blob + q.ent_off;
+    w.load(T, blob);
+    __syncthreads();
+    Reader rd;
+    Sink none{};
+    int b = 0, z = 0;
+    uint64_t cur = kDead;
+    if (valid) {
+        // cold: b = z = 0 (the first block of a restart unit, its first coefficient).  On the 00 of a stuffed pair or on the code of
+        // a marker, start behind it.
+        int start = j * kSubseq;
+        if (start > 0 && start < q.ent_len && ent[start - 1] == 0xFFu && (ent[start] == 0 || (ent[start] >= 0xD0u && ent[start] <= 0xD7u))) ++start;
+        rd.open(ent, q.ent_len, start);
+        int n = 0, r = 0;
+        cur = subseq_run<false>(w, T, rd, b, z, (uint32_t)(j + 1) * (kSubseq * 8u), n, r, none);
+        sN[t] = n; sR[t] = r;
+    }
+    sState[t] = cur;
+    bool active = valid && cur != kDead;
+    for (int step = 1; step < kLanes; ++step) {
+        __syncthreads();
+        const int tj = t + step;
+        const bool go = active && tj < kLanes && j + step < q.nsub;
+        if (!go) active = false;
+        if (go) {
+            int n = 0, r = 0;
+            const uint64_t ns = subseq_run<false>(w, T, rd, b, z, (uint32_t)(j + step + 1) * (kSubseq * 8u), n, r, none);
+            const uint64_t old = sState[tj];
+            sState[tj] = ns; sN[tj] = n; sR[tj] = r;
+            if (ns == kDead || ns == old) active = false;
+        }
+        if (!__syncthreads_or(active)) break;
+    }
+    __syncthreads();
+    if (valid) {
+        state[q.sub0 + j] = sState[t];
+        cnt_n[q.sub0 + j] = sN[t];
+        cnt_r[q.sub0 + j] = sR[t];
+    }
+}
+
+// grid (workgroups of the largest item, items), one wave; lane 0 carries the end state of the workgroup before this one into its own
+// subsequences until it meets the recorded state
+template <class P>
+__global__ __launch_bounds__(64) void k_js_sync_global(const uint8_t *__restrict__ blob, const typename P::Args a, uint64_t *state,
+                                                        int *__restrict__ cnt_n, int *__restrict__ cnt_r, int *__restrict__ flag) {
+    __shared__ typename P::Tables T;
+    const P w(a, blockIdx.y);
+    const auto &q = w.seq();
+    if (blockIdx.x == 0 || (int)blockIdx.x >= q.nwg) return;
+    w.load(T, blob);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int j0 = blockIdx.x * kLanes, j1 = min(j0 + kLanes, q.nsub);
+    // the state of the workgroup before this one may be rewritten while it is read here: either value is a state, and a rewrite
+    // raises the flag, so that this workgroup reads it again in the next launch
+    uint64_t st = __hip_atomic_load(state + q.sub0 + j0 - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (st == kDead) return;
+    Reader rd;
+    Sink none{};
+    int b, z;
+    open_at(w, rd, blob + q.ent_off, st, b, z);
+    for (int j = j0; j < j1; ++j) {
+        int n = 0, r = 0;
+        const uint64_t ns = subseq_run<false>(w, T, rd, b, z, (uint32_t)(j + 1) * (kSubseq * 8u), n, r, none);
+        const uint64_t old = state[q.sub0 + j];
+        cnt_n[q.sub0 + j] = n;
+        cnt_r[q.sub0 + j] = r;
+        if (ns == old) break;
+        __hip_atomic_store(state + q.sub0 + j, ns, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *flag = 1;
+        if (ns == kDead) break;
+    }
+}
+
 template <typename T> __device__ T block_exclusive(T v, T *sh) {
     const int t = threadIdx.x;
     sh[t] = v;
@@ -191,6 +377,131 @@ template <typename T> __device__ T block_exclusive(T v, T *sh) {
     const T ex = t ? sh[t - 1] : 0;
     __syncthreads();
     return ex;
+}
+
+// one workgroup per item: off_n / off_r = exclusive sums of cnt_n / cnt_r over the item's subsequences, the output position of each
+template <class P>
+__global__ __launch_bounds__(kLanes) void k_js_scan(const typename P::Args a, const int *__restrict__ cnt_n, const int *__restrict__ cnt_r,
+                                                     int64_t *__restrict__ off_n, int *__restrict__ off_r) {
+    __shared__ int64_t sh[kLanes];
+    const P w(a, blockIdx.x);
+    const auto &q = w.seq();
+    const int t = threadIdx.x;
+    const int per = (q.nsub + kLanes - 1) / kLanes, j0 = min(q.nsub, t * per), j1 = min(q.nsub, j0 + per);
+    int64_t sn = 0, sr = 0;
+    for (int j = j0; j < j1; ++j) { sn += cnt_n[q.sub0 + j]; sr += cnt_r[q.sub0 + j]; }
+    int64_t en = block_exclusive(sn, sh);
+    int64_t er = block_exclusive(sr, sh);
+    for (int j = j0; j < j1; ++j) {
+        off_n[q.sub0 + j] = en; off_r[q.sub0 + j] = (int)min(er, (int64_t)INT32_MAX);
+        en += cnt_n[q.sub0 + j]; er += cnt_r[q.sub0 + j];
+    }
+}
+
+// grid as k_js_sync_local.  Every lane decodes its subsequence once more from its entry state and stores the coefficients (the
+// buffer is zeroed before).  err bits: 1 an invalid code or a subsequence without a state, 2 the data do not hold the item's blocks
+// exactly
+template <class P>
+__global__ __launch_bounds__(kLanes) void k_js_write(const uint8_t *__restrict__ blob, const typename P::Args a,
+                                                      const uint64_t *__restrict__ state, const int *__restrict__ cnt_n,
+                                                      const int64_t *__restrict__ off_n, const int *__restrict__ off_r,
+                                                      int16_t *__restrict__ coef, int *__restrict__ err) {
+    __shared__ typename P::Tables T;
+    const P w(a, blockIdx.y);
+    const auto &q = w.seq();
+    if ((int)blockIdx.x >= q.nwg) return;
+    w.load(T, blob);
+    __syncthreads();
+    const int j = blockIdx.x * kLanes + threadIdx.x;
+    if (j >= q.nsub) return;
+    int *e = err + w.err_index(blockIdx.y);
+    const uint64_t st = j == 0 ? pack_state(0, 0, 0) : state[q.sub0 + j - 1];
+    if (st == kDead) { atomicOr(e, 1); return; }
+    Reader rd;
+    int b, z;
+    open_at(w, rd, blob + q.ent_off, st, b, z);
+    Sink sink{coef, off_n[q.sub0 + j], w.interval_slots(), off_r[q.sub0 + j]};
+    int n = 0, r = 0;
+    const uint64_t ns = subseq_run<true>(w, T, rd, b, z, (uint32_t)(j + 1) * (kSubseq * 8u), n, r, sink);
+    if (ns == kDead) atomicOr(e, 1);
+    if (j == q.nsub - 1 && off_n[q.sub0 + j] + cnt_n[q.sub0 + j] != w.total_slots()) atomicOr(e, 2);
+}
+
+// the scratch regions of the machine: Plan and PPlan lay them out under the same names
+struct Subseq {
+    uint64_t *state;
+    int *cnt_n, *cnt_r;
+    int64_t *off_n;
+    int *off_r, *flag;
+};
+
+template <class L> Subseq subseq_regions(char *S, const L &p) {
+    return {(uint64_t *)(S + p.o_state), (int *)(S + p.o_cnt_n), (int *)(S + p.o_cnt_r), (int64_t *)(S + p.o_off_n),
+            (int *)(S + p.o_off_r), (int *)(S + p.o_flag)};
+}
+
+// The machine over `items` work items that hold nsub subsequences together, the largest max_wg workgroups: k_js_sync_local,
+// k_js_sync_global relaunched until the flag stays clear (the host reads the 4-byte flag: one stream synchronise per pass; after more
+// passes than there are subsequences it gives up), k_js_scan, k_js_write.  `passes` counts the passes of the whole call: the caller
+// has cleared the flag before the first of them.
+template <class P>
+int subseq_decode(const uint8_t *blob, const typename P::Args &a, int items, int max_wg, int64_t nsub, const Subseq &q, int16_t *coef,
+                  int *err, int &passes, hipStream_t st) {
+    const dim3 grid((unsigned)max_wg, (unsigned)items);
+    k_js_sync_local<P><<<grid, kLanes, 0, st>>>(blob, a, q.state, q.cnt_n, q.cnt_r);
+    int rc = csm::check_launch("k_js_sync_local"); if (rc) return rc;
+    if (max_wg > 1) {
+        for (int own = 0;; ++own) {
+            if (own > nsub) {
+                (void)hipStreamSynchronize(st);
+                csm::set_error("jpeg decode: the subsequence states did not settle in %d passes", own);
+                return CSM_ERR_DATA;
+            }
+            int changed = 0;
+            if (passes) CSM_HIP(hipMemsetAsync(q.flag, 0, 4, st));
+            k_js_sync_global<P><<<grid, 64, 0, st>>>(blob, a, q.state, q.cnt_n, q.cnt_r, q.flag);
+            rc = csm::check_launch("k_js_sync_global"); if (rc) return rc;
+            CSM_HIP(hipMemcpyAsync(&changed, q.flag, 4, hipMemcpyDeviceToHost, st));
+            CSM_HIP(hipStreamSynchronize(st));
+            ++passes;
+            if (!changed) break;
+        }
+    }
+    k_js_scan<P><<<items, kLanes, 0, st>>>(a, q.cnt_n, q.cnt_r, q.off_n, q.off_r);
+    rc = csm::check_launch("k_js_scan"); if (rc) return rc;
+    k_js_write<P><<<grid, kLanes, 0, st>>>(blob, a, q.state, q.cnt_n, q.off_n, q.off_r, coef, err);
+    return csm::check_launch("k_js_write");
+}
+
+// ---- DC prediction ------------------------------------------------------------------------------------------------------------
+// By a whole workgroup of kLanes: the DC differences at C[addr(k)], k in [0, total) in the scan order of one component, become
+// values << al; the sum restarts where resets(k).  A thread sums a run of consecutive blocks; the runs are joined by a segmented scan.
+template <class Addr, class Resets> __device__ __forceinline__ void dc_predict(int16_t *C, int total, int al, Addr addr, Resets resets) {
+    __shared__ int sSum[kLanes];
+    __shared__ int sFlag[kLanes];
+    const int t = threadIdx.x;
+    const int per = (total + kLanes - 1) / kLanes, k0 = min(total, t * per), k1 = min(total, k0 + per);
+    int sum = 0, flag = 0;
+    for (int k = k0; k < k1; ++k) {
+        if (resets(k)) { sum = 0; flag = 1; }
+        sum += C[addr(k)];
+    }
+    sSum[t] = sum; sFlag[t] = flag;
+    __syncthreads();
+    for (int d = 1; d < kLanes; d <<= 1) {           // inclusive segmented scan: (a, fa) . (b, fb) = (fb ? b : a + b, fa | fb)
+        int s = sSum[t], fl = sFlag[t];
+        if (t >= d) { if (!fl) s += sSum[t - d]; fl |= sFlag[t - d]; }
+        __syncthreads();
+        sSum[t] = s; sFlag[t] = fl;
+        __syncthreads();
+    }
+    int run = t ? sSum[t - 1] : 0;
+    for (int k = k0; k < k1; ++k) {
+        if (resets(k)) run = 0;
+        const int64_t at = addr(k);
+        run += C[at];
+        C[at] = (int16_t)(run * (1 << al));
+    }
 }
 
 // ---- inverse DCT ------------------------------------------------------------------------------------------------------------

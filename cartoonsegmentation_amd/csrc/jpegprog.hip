@@ -7,10 +7,12 @@
 // A work item is a (file, scan) pair.  The host orders the scans by dependency level (the scans of one level write disjoint
 // coefficients) and launches one group of kernels per level over all files of the call.
 //
-//   first scans (ah = 0): the subsequence machine of jpegdec.hip; a lane's state is (bit position, block of the restart unit) in a
-//   DC scan and (bit position, k - ss) in an AC scan.  An EOBn symbol takes the rest of its block and `run` whole bands of slots at
-//   once: the run uses no further bits and is no part of the state, so the scan still synchronises by itself.
-//     k_pj_sync_local, k_pj_sync_global (relaunched by the host until a device flag stays clear), k_pj_scan, k_pj_write
+//   first scans (ah = 0): the subsequence machine of csm_jpeg.h under the policy `FirstScan` below; a lane's state is (bit position,
+//   block of the restart unit) in a DC scan and (bit position, k - ss) in an AC scan.  An EOBn symbol takes the rest of its block
+//   and `run` whole bands of slots at once: the run uses no further bits and is no part of the state, so the scan still
+//   synchronises by itself.
+//     k_js_sync_local<FirstScan>, k_js_sync_global<FirstScan> (relaunched by the host until a device flag stays clear),
+//     k_js_scan<FirstScan>, k_js_write<FirstScan>
 //     k_pj_dc       DC first scans: differences -> values per component (restarting at every restart interval), then << al
 //   refinements (ah = al + 1): the correction bits between two symbols of an AC refinement depend on the block's history, so a
 //   lane that does not know its block can never find it: one lane decodes one restart interval of one scan, serially.
@@ -123,31 +125,7 @@ bool make_scan_plan(const Plan &p, const int32_t *sdesc, int n_scans, int64_t bl
     return true;
 }
 
-struct PTables {                // of one scan, in LDS: jpegcode.scan_tables
-    uint32_t w[kScanTables * kTableBytes / 4];
-    __device__ __forceinline__ const uint16_t *lut(int s) const { return (const uint16_t *)((const uint8_t *)w + s * kTableBytes); }
-    __device__ __forceinline__ const int *maxcode(int s) const { return (const int *)((const uint8_t *)w + s * kTableBytes + 512); }
-    __device__ __forceinline__ const int *valoff(int s) const { return (const int *)((const uint8_t *)w + s * kTableBytes + 584); }
-    __device__ __forceinline__ const uint8_t *vals(int s) const { return (const uint8_t *)w + s * kTableBytes + 656; }
-};
-
-__device__ __forceinline__ void load_scan_tables(PTables &T, const uint8_t *blob, const PScan &s) {
-    const uint32_t *src = (const uint32_t *)(blob + s.tab_off);
-    for (int i = threadIdx.x; i < s.ntab * (kTableBytes / 4); i += blockDim.x) T.w[i] = src[i];
-}
-
-// the code at the top of v (the next 32 bits) in table `slot`: false for an invalid code
-__device__ __forceinline__ bool huff_decode(const PTables &T, int slot, uint32_t v, int &ln, int &sym) {
-    const uint32_t e = T.lut(slot)[v >> 24];
-    if (e) { ln = (int)(e >> 8); sym = (int)(e & 255u); return true; }
-    const int *mc = T.maxcode(slot);
-    const int code16 = (int)(v >> 16);
-    int c = 0;
-    for (ln = 9; ln <= 16; ++ln) { c = code16 >> (16 - ln); if (c <= mc[ln]) break; }
-    if (ln > 16) return false;
-    sym = T.vals(slot)[(T.valoff(slot)[ln] + c) & 255];
-    return true;
-}
+using ScanTables = HuffTables<kScanTables>;     // of one scan, in LDS: jpegcode.scan_tables
 
 // store index (MCU-interleaved order of the file) of block i (< s.nblk) of the scan
 __device__ __forceinline__ int store_index(const JFile &f, const PScan &s, int i) {
@@ -158,275 +136,75 @@ __device__ __forceinline__ int store_index(const JFile &f, const PScan &s, int i
     return ((by / v) * f.mx + bx / h) * f.bpm + first + (by % v) * h + (bx % h);
 }
 
-__device__ __forceinline__ uint64_t pack_state(uint32_t p, int b, int z) { return ((uint64_t)p << 16) | ((uint64_t)b << 8) | (uint64_t)z; }
-
-struct PSink {
-    int16_t *coef;       // the file's blocks
-    int64_t slot;        // slot of the current state
-    int64_t per_marker;  // slots of a restart interval
-    int marks_before;
+// ---- first scans ------------------------------------------------------------------------------------------------------------------
+// The machine's policy for a first scan.  DC scan: b = block of the restart unit, one symbol (its size) and one slot per block.  AC
+// scan: z = k - ss; a slot is one coefficient of the band of one block, blocks in scan order; a symbol (run, size) takes run + 1
+// slots, ZRL 16, EOBn the rest of its block and (1 << n) - 1 + its n extra bits further bands.
+struct FirstScan {
+    using Tables = ScanTables;
+    struct Args { const JFile *files; const PScan *scans; };       // scans: the first scans of the level
+    const PScan s;
+    const JFile f;
+    __device__ FirstScan(const Args &a, int item) : s(a.scans[item]), f(a.files[s.file]) {}
+    __device__ const PScan &seq() const { return s; }
+    __device__ void load(Tables &T, const uint8_t *blob) const { load_tables(T, blob + s.tab_off, s.ntab); }
+    __device__ int table(int b, int) const { return s.ss == 0 && s.ns > 1 ? (b < s.bpu - 2 ? 0 : b - (s.bpu - 3)) : 0; }
+    __device__ bool symbol(int sym, int z, Symbol &y) const {
+        if (s.ss == 0) { y.size = y.extra = sym; y.adv = 1; return sym <= 11; }
+        const int run = sym >> 4;
+        y.size = y.extra = sym & 15;
+        if (y.size == 0) {
+            if (run == 15) y.adv = 16;
+            else { y.adv = 0; y.extra = run; }          // EOBn: what it takes follows from its extra bits (advance)
+        } else {
+            if (y.size > 10) return false;
+            y.adv = run + 1;
+        }
+        return z + y.adv <= s.L;
+    }
+    __device__ int advance(const Symbol &y, int bits, int &b, int &z) const {
+        if (s.ss == 0) { b = b + 1 < s.bpu ? b + 1 : 0; return 1; }
+        const int adv = y.adv ? y.adv : (s.L - z) + ((1 << y.extra) - 1 + bits) * s.L;          // at most 32767 * 63 + 63
+        z += adv;
+        if (!y.adv || z >= s.L) z = 0;
+        return adv;
+    }
+    __device__ void clamp(int &b, int &z) const {
+        if (b >= s.bpu || s.ss > 0) b = 0;
+        if (z >= s.L) z = 0;
+    }
+    __device__ void store(int16_t *coef, int64_t at, int val) const {
+        const int64_t blk = at / s.L;
+        if (at < 0 || blk >= s.nblk) return;
+        const int k = s.ss + (int)(at - blk * s.L);
+        // a DC difference is stored as it is: k_pj_dc sums and shifts
+        coef[(f.blk0 + store_index(f, s, (int)blk)) * 64 + kNatural[k]] = (int16_t)(s.ss == 0 ? val : val * (1 << s.al));
+    }
+    __device__ int64_t interval_slots() const { return (int64_t)s.ri * s.bpu * s.L; }
+    __device__ int64_t total_slots() const { return (int64_t)s.nblk * s.L; }
+    __device__ int err_index(int) const { return s.file; }
 };
 
-// Decodes symbols of a first scan from (rd, b, z) while the next symbol begins before bit `limit` of the scan's entropy bytes.
-// Returns the packed end state, kDead after an invalid code.  n_slots / n_mark count the coefficient slots and the restart markers
-// passed.  A slot is one coefficient of the band of one block, blocks in scan order.
-template <bool EMIT>
-__device__ uint64_t pj_run(Reader &rd, int &b, int &z, uint32_t limit, const JFile &f, const PScan &s, const PTables &T, int &n_slots,
-                           int &n_mark, PSink &sink) {
-    const bool dc = s.ss == 0;
-    for (;;) {
-        rd.refill();
-        bool marker = rd.at_marker();
-        int adv = 0, sz = 0, extra = 0, total = 0, run = 0;
-        bool eob = false;
-        uint32_t v = 0;
-        if (!marker) {
-            if (rd.bitpos() >= limit) return pack_state(rd.bitpos(), b, z);
-            v = (uint32_t)(rd.win >> 32);
-            int ln, sym;
-            if (!huff_decode(T, dc && s.ns > 1 ? (b < s.bpu - 2 ? 0 : b - (s.bpu - 3)) : 0, v, ln, sym)) return kDead;
-            if (dc) {
-                sz = extra = sym; adv = 1;
-                if (sz > 11) return kDead;
-            } else {
-                run = sym >> 4;
-                sz = extra = sym & 15;
-                if (sz == 0) {
-                    if (run == 15) adv = 16;
-                    else { eob = true; extra = run; }
-                } else {
-                    if (sz > 10) return kDead;
-                    adv = run + 1;
-                }
-                if (z + adv > s.L) return kDead;
-            }
-            total = ln + extra;                  // at most 16 + 15 bits
-            marker = total > rd.nb;              // the symbol runs into a marker or the end: not a symbol
-        }
-        if (marker) {
-            if (rd.stop != 1) { b = 0; z = 0; return pack_state((uint32_t)s.ent_len * 8u, 0, 0); }
-            rd.cross();
-            b = 0; z = 0;
-            ++n_mark;
-            if constexpr (EMIT) sink.slot = (int64_t)(sink.marks_before + n_mark) * sink.per_marker;
-            continue;
-        }
-        const int bits = extra ? (int)((v >> (32 - total)) & ((1u << extra) - 1u)) : 0;
-        if (eob) adv = (s.L - z) + ((1 << run) - 1 + bits) * s.L;           // at most 32767 * 63 + 63
-        if constexpr (EMIT) {
-            if (sz && !eob) {
-                int val = bits;
-                if (val < (1 << (sz - 1))) val -= (1 << sz) - 1;
-                const int64_t at = sink.slot + adv - 1;
-                const int64_t blk = at / s.L;
-                if (at >= 0 && blk < s.nblk) {
-                    const int k = s.ss + (int)(at - blk * s.L);
-                    // a DC difference is stored as it is: k_pj_dc sums and shifts
-                    sink.coef[(int64_t)store_index(f, s, (int)blk) * 64 + kNatural[k]] = (int16_t)(dc ? val : val * (1 << s.al));
-                }
-            }
-            sink.slot += adv;
-        }
-        rd.skip(total);
-        n_slots += adv;
-        if (dc) b = b + 1 < s.bpu ? b + 1 : 0;
-        else { z += adv; if (eob || z >= s.L) z = 0; }
-    }
-}
-
-// a reader at the packed state st (not kDead) of the scan
-__device__ __forceinline__ void open_at(Reader &rd, const uint8_t *ent, const PScan &s, uint64_t st, int &b, int &z) {
-    const uint32_t p = (uint32_t)(st >> 16);
-    b = (int)((st >> 8) & 255u); z = (int)(st & 255u);
-    if (b >= s.bpu || s.ss > 0) b = 0;
-    if (z >= s.L) z = 0;
-    rd.open(ent, s.ent_len, (int)min(p >> 3, (uint32_t)s.ent_len));
-    rd.refill();
-    const int off = (int)(p & 7u);
-    if (off < rd.nb) rd.skip(off);
-}
-
-// ---- first scans: synchronisation ---------------------------------------------------------------------------------------------
-// grid (workgroups of the largest scan, first scans of the level); lane = one subsequence
-__global__ __launch_bounds__(kLanes) void k_pj_sync_local(const uint8_t *__restrict__ blob, const JFile *__restrict__ files,
-                                                           const PScan *__restrict__ scans, uint64_t *__restrict__ state,
-                                                           int *__restrict__ cnt_n, int *__restrict__ cnt_r) {
-    __shared__ PTables T;
-    __shared__ uint64_t sState[kLanes];
-    __shared__ int sN[kLanes], sR[kLanes];
-    const PScan s = scans[blockIdx.y];
-    if ((int)blockIdx.x >= s.nwg) return;
-    const JFile f = files[s.file];
-    const int t = threadIdx.x, j = blockIdx.x * kLanes + t;
-    const bool valid = j < s.nsub;
-    const uint8_t *ent = blob + s.ent_off;
-    load_scan_tables(T, blob, s);
-    __syncthreads();
-    Reader rd;
-    PSink none{};
-    int b = 0, z = 0;
-    uint64_t cur = kDead;
-    if (valid) {
-        // cold: block 0 of a restart unit, first coefficient of the band.  On the 00 of a stuffed pair or on the code of a marker,
-        // start behind it.
-        int start = j * kSubseq;
-        if (start > 0 && start < s.ent_len && ent[start - 1] == 0xFFu && (ent[start] == 0 || (ent[start] >= 0xD0u && ent[start] <= 0xD7u))) ++start;
-        rd.open(ent, s.ent_len, start);
-        int n = 0, r = 0;
-        cur = pj_run<false>(rd, b, z, (uint32_t)(j + 1) * (kSubseq * 8u), f, s, T, n, r, none);
-        sN[t] = n; sR[t] = r;
-    }
-    sState[t] = cur;
-    bool active = valid && cur != kDead;
-    for (int step = 1; step < kLanes; ++step) {
-        __syncthreads();
-        const int tj = t + step;
-        const bool go = active && tj < kLanes && j + step < s.nsub;
-        if (!go) active = false;
-        if (go) {
-            int n = 0, r = 0;
-            const uint64_t ns = pj_run<false>(rd, b, z, (uint32_t)(j + step + 1) * (kSubseq * 8u), f, s, T, n, r, none);
-            const uint64_t old = sState[tj];
-            sState[tj] = ns; sN[tj] = n; sR[tj] = r;
-            if (ns == kDead || ns == old) active = false;
-        }
-        if (!__syncthreads_or(active)) break;
-    }
-    __syncthreads();
-    if (valid) {
-        state[s.sub0 + j] = sState[t];
-        cnt_n[s.sub0 + j] = sN[t];
-        cnt_r[s.sub0 + j] = sR[t];
-    }
-}
-
-// grid (workgroups of the largest scan, first scans of the level), one wave; lane 0 carries the state across the workgroup's first
-// boundary
-__global__ __launch_bounds__(64) void k_pj_sync_global(const uint8_t *__restrict__ blob, const JFile *__restrict__ files,
-                                                        const PScan *__restrict__ scans, uint64_t *state, int *__restrict__ cnt_n,
-                                                        int *__restrict__ cnt_r, int *__restrict__ flag) {
-    __shared__ PTables T;
-    const PScan s = scans[blockIdx.y];
-    if (blockIdx.x == 0 || (int)blockIdx.x >= s.nwg) return;
-    const JFile f = files[s.file];
-    load_scan_tables(T, blob, s);
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const int j0 = blockIdx.x * kLanes, j1 = min(j0 + kLanes, s.nsub);
-    // the state of the workgroup before this one may be rewritten while it is read here: either value is a state, and a rewrite
-    // raises the flag, so that this workgroup reads it again in the next launch
-    uint64_t st = __hip_atomic_load(state + s.sub0 + j0 - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (st == kDead) return;
-    Reader rd;
-    PSink none{};
-    int b, z;
-    open_at(rd, blob + s.ent_off, s, st, b, z);
-    for (int j = j0; j < j1; ++j) {
-        int n = 0, r = 0;
-        const uint64_t ns = pj_run<false>(rd, b, z, (uint32_t)(j + 1) * (kSubseq * 8u), f, s, T, n, r, none);
-        const uint64_t old = state[s.sub0 + j];
-        cnt_n[s.sub0 + j] = n;
-        cnt_r[s.sub0 + j] = r;
-        if (ns == old) break;
-        __hip_atomic_store(state + s.sub0 + j, ns, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *flag = 1;
-        if (ns == kDead) break;
-    }
-}
-
-// one workgroup per first scan: off_n / off_r = exclusive sums of cnt_n / cnt_r over the scan's subsequences
-__global__ __launch_bounds__(kLanes) void k_pj_scan(const PScan *__restrict__ scans, const int *__restrict__ cnt_n, const int *__restrict__ cnt_r,
-                                                     int64_t *__restrict__ off_n, int *__restrict__ off_r) {
-    __shared__ int64_t sh[kLanes];
-    const PScan s = scans[blockIdx.x];
-    const int t = threadIdx.x;
-    const int per = (s.nsub + kLanes - 1) / kLanes, j0 = min(s.nsub, t * per), j1 = min(s.nsub, j0 + per);
-    int64_t sn = 0, sr = 0;
-    for (int j = j0; j < j1; ++j) { sn += cnt_n[s.sub0 + j]; sr += cnt_r[s.sub0 + j]; }
-    int64_t en = block_exclusive(sn, sh);
-    int64_t er = block_exclusive(sr, sh);
-    for (int j = j0; j < j1; ++j) {
-        off_n[s.sub0 + j] = en; off_r[s.sub0 + j] = (int)min(er, (int64_t)INT32_MAX);
-        en += cnt_n[s.sub0 + j]; er += cnt_r[s.sub0 + j];
-    }
-}
-
-// err bits: 1 an invalid code or a subsequence without a state, 2 the data do not hold the scan's blocks exactly, 4 an invalid
-// symbol of a refinement scan (a size above 1, a coefficient placed past the band)
-__global__ __launch_bounds__(kLanes) void k_pj_write(const uint8_t *__restrict__ blob, const JFile *__restrict__ files,
-                                                      const PScan *__restrict__ scans, const uint64_t *__restrict__ state,
-                                                      const int *__restrict__ cnt_n, const int64_t *__restrict__ off_n,
-                                                      const int *__restrict__ off_r, int16_t *__restrict__ coef, int *__restrict__ err) {
-    __shared__ PTables T;
-    const PScan s = scans[blockIdx.y];
-    if ((int)blockIdx.x >= s.nwg) return;
-    const JFile f = files[s.file];
-    load_scan_tables(T, blob, s);
-    __syncthreads();
-    const int j = blockIdx.x * kLanes + threadIdx.x;
-    if (j >= s.nsub) return;
-    const uint64_t st = j == 0 ? pack_state(0, 0, 0) : state[s.sub0 + j - 1];
-    if (st == kDead) { atomicOr(err + s.file, 1); return; }
-    Reader rd;
-    int b, z;
-    open_at(rd, blob + s.ent_off, s, st, b, z);
-    PSink sink;
-    sink.coef = coef + f.blk0 * 64;
-    sink.slot = off_n[s.sub0 + j];
-    sink.per_marker = (int64_t)s.ri * s.bpu * s.L;
-    sink.marks_before = off_r[s.sub0 + j];
-    int n = 0, r = 0;
-    const uint64_t ns = pj_run<true>(rd, b, z, (uint32_t)(j + 1) * (kSubseq * 8u), f, s, T, n, r, sink);
-    if (ns == kDead) atomicOr(err + s.file, 1);
-    if (j == s.nsub - 1 && off_n[s.sub0 + j] + cnt_n[s.sub0 + j] != (int64_t)s.nblk * s.L) atomicOr(err + s.file, 2);
-}
-
-// ---- DC first scans: prediction -------------------------------------------------------------------------------------------------
 // grid (components, first scans of the level): the DC differences of one component in scan order become values, << al; the sum
-// restarts at every restart interval.  A thread sums a run of consecutive blocks; the runs are joined by a segmented scan.
+// restarts at every restart interval
 __global__ __launch_bounds__(kLanes) void k_pj_dc(const JFile *__restrict__ files, const PScan *__restrict__ scans, int16_t *__restrict__ coef) {
-    __shared__ int sSum[kLanes];
-    __shared__ int sFlag[kLanes];
     const PScan s = scans[blockIdx.y];
     if (s.ss != 0 || (int)blockIdx.x >= s.ns) return;
     const JFile f = files[s.file];
-    const int t = threadIdx.x;
     const bool inter = s.ns > 1;
     const int c = inter ? (int)blockIdx.x : s.comp;
     const int ysub = f.nc == 1 ? 1 : f.hs * f.vs;
     const int nbc = inter && c == 0 ? ysub : 1, first = c == 0 ? 0 : ysub + c - 1;
-    const int total = inter ? f.mx * f.my * nbc : s.nblk;
     const int every = s.ri * nbc;                       // blocks of this component in a restart interval
-    int16_t *C = coef + f.blk0 * 64;
-    const int per = (total + kLanes - 1) / kLanes, k0 = min(total, t * per), k1 = min(total, k0 + per);
-    auto addr = [&](int k) -> int64_t {
-        if (!inter) return (int64_t)store_index(f, s, k) * 64;
-        const int m = k / nbc, sb = k - m * nbc;
-        return ((int64_t)m * f.bpm + first + sb) * 64;
-    };
-    auto resets = [&](int k) { return every > 0 && k % every == 0; };
-    int sum = 0, flag = 0;
-    for (int k = k0; k < k1; ++k) {
-        if (resets(k)) { sum = 0; flag = 1; }
-        sum += C[addr(k)];
-    }
-    sSum[t] = sum; sFlag[t] = flag;
-    __syncthreads();
-    for (int d = 1; d < kLanes; d <<= 1) {           // inclusive segmented scan: (a, fa) . (b, fb) = (fb ? b : a + b, fa | fb)
-        int v = sSum[t], fl = sFlag[t];
-        if (t >= d) { if (!fl) v += sSum[t - d]; fl |= sFlag[t - d]; }
-        __syncthreads();
-        sSum[t] = v; sFlag[t] = fl;
-        __syncthreads();
-    }
-    int run = t ? sSum[t - 1] : 0;
-    for (int k = k0; k < k1; ++k) {
-        if (resets(k)) run = 0;
-        const int64_t a = addr(k);
-        run += C[a];
-        C[a] = (int16_t)(run * (1 << s.al));
-    }
+    dc_predict(coef + f.blk0 * 64, inter ? f.mx * f.my * nbc : s.nblk, s.al,
+               [&](int k) -> int64_t {
+                   if (!inter) return (int64_t)store_index(f, s, k) * 64;
+                   const int m = k / nbc, sb = k - m * nbc;
+                   return ((int64_t)m * f.bpm + first + sb) * 64;
+               },
+               [&](int k) { return every > 0 && k % every == 0; });
 }
+
 
 // ---- refinements ------------------------------------------------------------------------------------------------------------------
 // The serial decode never touches a coefficient: per block of an AC refinement it reads one 64-bit history mask and writes three
@@ -491,9 +269,9 @@ __device__ __forceinline__ void touch(const void *p) {
 __global__ __launch_bounds__(kLanes) void k_pj_refine(const uint8_t *__restrict__ blob, const JFile *__restrict__ files,
                                                        const PScan *__restrict__ scans, uint64_t *__restrict__ rec_all,
                                                        int *__restrict__ err) {
-    __shared__ PTables T;
+    __shared__ ScanTables T;
     const PScan s = scans[blockIdx.y];
-    load_scan_tables(T, blob, s);
+    load_tables(T, blob + s.tab_off, s.ntab);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = blockIdx.x * (kLanes / 64) + (threadIdx.x >> 6), waves = gridDim.x * (kLanes / 64);
     const int per = s.nint > 1 ? s.ri * s.bpu : s.nblk;             // blocks of a restart interval
@@ -640,16 +418,13 @@ extern "C" int csm_jpeg_decode_progressive(const uint8_t *blob, int64_t blob_byt
     int16_t *coef = (int16_t *)(S + p.o_coef);
     uint8_t *planes = (uint8_t *)(S + p.o_planes);
     PScan *scans = (PScan *)(S + q.o_scans);
-    uint64_t *state = (uint64_t *)(S + q.o_state);
-    int *cnt_n = (int *)(S + q.o_cnt_n), *cnt_r = (int *)(S + q.o_cnt_r), *off_r = (int *)(S + q.o_off_r);
-    int64_t *off_n = (int64_t *)(S + q.o_off_n);
+    const Subseq sub = subseq_regions(S, q);
     uint64_t *mask = (uint64_t *)(S + q.o_mask);
-    int *flag = (int *)(S + q.o_flag);
     // the descriptors live in p and q until this call returns, and it returns only after the stream has drained (below)
     CSM_HIP(hipMemcpyAsync(files, p.files.data(), (size_t)n * sizeof(JFile), hipMemcpyHostToDevice, st));
     CSM_HIP(hipMemcpyAsync(scans, q.scans.data(), (size_t)n_scans * sizeof(PScan), hipMemcpyHostToDevice, st));
     CSM_HIP(hipMemsetAsync(S + p.o_flag, 0, (size_t)(p.o_coef - p.o_flag) + (size_t)csm::align16(p.blocks * 128), st));   // flag, err, coefficients
-    CSM_HIP(hipMemsetAsync(flag, 0, 16, st));
+    CSM_HIP(hipMemsetAsync(sub.flag, 0, 16, st));
     int passes = 0, levels = 0, rc;
     int i = 0;
     while (i < n_scans) {
@@ -663,30 +438,7 @@ extern "C" int csm_jpeg_decode_progressive(const uint8_t *blob, int64_t blob_byt
         if (m > i) {
             int max_wg = 0, level_sub = 0;
             for (int k = i; k < m; ++k) { max_wg = std::max(max_wg, q.scans[k].nwg); level_sub += q.scans[k].nsub; }
-            const dim3 grid((unsigned)max_wg, (unsigned)(m - i));
-            k_pj_sync_local<<<grid, kLanes, 0, st>>>(blob, files, scans + i, state, cnt_n, cnt_r);
-            rc = csm::check_launch("k_pj_sync_local"); if (rc) return rc;
-            if (max_wg > 1) {
-                for (int level_passes = 0;; ++level_passes) {
-                    if (level_passes > level_sub) {
-                        (void)hipStreamSynchronize(st);
-                        csm::set_error("jpeg decode: the subsequence states did not settle in %d passes", level_passes);
-                        return CSM_ERR_DATA;
-                    }
-                    int changed = 0;
-                    if (passes) CSM_HIP(hipMemsetAsync(flag, 0, 4, st));
-                    k_pj_sync_global<<<grid, 64, 0, st>>>(blob, files, scans + i, state, cnt_n, cnt_r, flag);
-                    rc = csm::check_launch("k_pj_sync_global"); if (rc) return rc;
-                    CSM_HIP(hipMemcpyAsync(&changed, flag, 4, hipMemcpyDeviceToHost, st));
-                    CSM_HIP(hipStreamSynchronize(st));
-                    ++passes;
-                    if (!changed) break;
-                }
-            }
-            k_pj_scan<<<m - i, kLanes, 0, st>>>(scans + i, cnt_n, cnt_r, off_n, off_r);
-            rc = csm::check_launch("k_pj_scan"); if (rc) return rc;
-            k_pj_write<<<grid, kLanes, 0, st>>>(blob, files, scans + i, state, cnt_n, off_n, off_r, coef, err);
-            rc = csm::check_launch("k_pj_write"); if (rc) return rc;
+            rc = subseq_decode<FirstScan>(blob, {files, scans + i}, m - i, max_wg, level_sub, sub, coef, err, passes, st); if (rc) return rc;
             k_pj_dc<<<dim3(3, (unsigned)(m - i)), kLanes, 0, st>>>(files, scans + i, coef);
             rc = csm::check_launch("k_pj_dc"); if (rc) return rc;
         }

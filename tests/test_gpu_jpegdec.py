@@ -40,6 +40,7 @@ def test_the_largest_case_spans_workgroups():
     for c in big:
         s, e = jpegcode.probe(C.case_file(c))['entropy']
         assert (e - s) / S > 256, C.case_id(c)
+    assert any(c['restart'] != 'none' for c in big)             # marker counts carried across a workgroup boundary
     stats = {}
     ops.jpeg_decode([C.case_file(big[0])], stats=stats)
     assert stats['passes'][0] >= 1

@@ -46,6 +46,18 @@ def test_a_first_scan_that_spans_two_workgroups():
     assert np.array_equal(t.cpu().numpy(), C.pil_decode(data))
 
 
+def test_restart_markers_counted_across_a_workgroup_boundary():
+    """a first scan of more than one workgroup with a restart marker every 2 blocks: the write pass places the second workgroup's
+    slots by the marker counts of the first"""
+    data = C.progressive_jpeg(C.frame('noise', 112, 112, 7), '444', 100, restart_marker_blocks=2)
+    info = jpegcode.probe(data, progressive=True)
+    assert max(s['entropy'][1] - s['entropy'][0] for s in info['scans'] if s['ah'] == 0) > WORKGROUP_BYTES
+    stats = {}
+    t = ops.jpeg_decode(data, progressive=True, stats=stats)
+    assert stats['progressive_passes'][0] >= 1
+    assert np.array_equal(t.cpu().numpy(), C.pil_decode(data))
+
+
 @pytest.mark.parametrize('grey, dc_bytes', [(200, 4128), (90, 8256)])
 def test_a_flat_grey_file_with_capped_eob_runs(grey, dc_bytes):
     """33024 blocks: the AC scans are one EOB run at the cap of 32767 blocks and a remainder, the DC refinement is 33024 bits: all
