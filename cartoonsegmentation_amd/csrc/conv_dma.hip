@@ -247,18 +247,11 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma(ConvArgs a) {
             const int mb = m0 + 32 * (TM * wm + i) + 4 * lh;
             float *ob = a.out.p + (int64_t)mb * ldo + cout_off + n;
             const float *rb = a.res_mode ? a.res.p + (int64_t)mb * ldr + cout_off + n : nullptr;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mo = (r & 3) + 8 * (r >> 2), m = mb + mo;
-                if (m >= a.M) continue;
-                float v = acc[i][j][r];
-                if constexpr (SER) v = tot[i][j][r] + v;
-                if (!SER && a.ksplit > 1) { a.partial[((int64_t)m * a.ksplit + ks) * a.cout_g + n] = v; continue; }
-                if (a.res_mode == 1) v += rb[mo * ldr];
-                v = apply_act(v, a.act, slope);
-                if (a.res_mode == 2) v += rb[mo * ldr];
-                ob[mo * ldo] = v;
-            }
+            auto val = [&](int r) { if constexpr (SER) return tot[i][j][r] + acc[i][j][r]; else return acc[i][j][r]; };
+            auto ok = [&](int r) { return mb + (r & 3) + 8 * (r >> 2) < a.M; };
+            auto eo = [](int r) { return (int64_t)((r & 3) + 8 * (r >> 2)); };
+            if (!SER && a.ksplit > 1) conv_tail_partial<16>(a.partial + ((int64_t)mb * a.ksplit + ks) * a.cout_g + n, (int64_t)a.ksplit * a.cout_g, val, ok, eo);
+            else conv_tail<16>(a, slope, ob, ldo, rb, ldr, val, ok, eo);
         }
     }
 }
@@ -482,17 +475,9 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma_p(ConvArgs a, int n_n
                 const int mb = m0 + 32 * (TM * wm + i) + 4 * lh;
                 float *ob = a.out.p + (int64_t)mb * ldo + cout_off + n;
                 const float *rb = a.res_mode ? a.res.p + (int64_t)mb * ldr + cout_off + n : nullptr;
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) {
-                    const int mo = (rr & 3) + 8 * (rr >> 2), m = mb + mo;
-                    if (m >= a.M) continue;
-                    float v = acc[i][jj][rr];
-                    if constexpr (SER) v = tot[i][jj][rr] + v;
-                    if (a.res_mode == 1) v += rb[mo * ldr];
-                    v = apply_act(v, a.act, slope);
-                    if (a.res_mode == 2) v += rb[mo * ldr];
-                    ob[mo * ldo] = v;
-                }
+                conv_tail<16>(a, slope, ob, ldo, rb, ldr,
+                              [&](int rr) { if constexpr (SER) return tot[i][jj][rr] + acc[i][jj][rr]; else return acc[i][jj][rr]; },
+                              [&](int rr) { return mb + (rr & 3) + 8 * (rr >> 2) < a.M; }, [](int rr) { return (int64_t)((rr & 3) + 8 * (rr >> 2)); });
             }
         }
     }

@@ -227,20 +227,19 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 8 ? 4 : 2)) void k_conv_m
         int n = n0 + MT * (TN * wn + tn) + li;
         if (n >= a.cout_g) continue;
         float slope = a.slope ? a.slope[cout_off + n] : 0.0f;
+        const int mb = m0 + MT * wm + 4 * lh;
+        auto val = [&](int r) { if constexpr (SER) return tot[tn][r] + acc[tn][r]; else return acc[tn][r]; };
+        auto eo = [](int r) { return (int64_t)(MT == 32 ? (r & 3) + 8 * (r >> 2) : r); };
+        auto ok = [&](int r) { return mb + (MT == 32 ? (r & 3) + 8 * (r >> 2) : r) < a.M; };
+        if (CSM_DBG(a) & 8) {
 #pragma unroll
-        for (int r = 0; r < NACC; ++r) {
-            int row = MT == 32 ? (r & 3) + 8 * (r >> 2) + 4 * lh : 4 * lh + r;
-            int m = m0 + MT * wm + row;
-            if (m >= a.M) continue;
-            float v = acc[tn][r];
-            if constexpr (SER) v = tot[tn][r] + v;
-            if (CSM_DBG(a) & 8) { if (v == 123.456f) a.out.p[0] = v; continue; }
-            if (!SER && a.ksplit > 1) { a.partial[((int64_t)m * a.ksplit + ks) * a.cout_g + n] = v; continue; }
-            if (a.res_mode == 1) v += a.res.p[(int64_t)m * a.res.ld + cout_off + n];
-            v = apply_act(v, a.act, slope);
-            if (a.res_mode == 2) v += a.res.p[(int64_t)m * a.res.ld + cout_off + n];
-            a.out.p[(int64_t)m * a.out.ld + cout_off + n] = v;
-        }
+            for (int r = 0; r < NACC; ++r)
+                if (ok(r) && val(r) == 123.456f) a.out.p[0] = val(r);
+        } else if (!SER && a.ksplit > 1)
+            conv_tail_partial<NACC>(a.partial + ((int64_t)mb * a.ksplit + ks) * a.cout_g + n, (int64_t)a.ksplit * a.cout_g, val, ok, eo);
+        else
+            conv_tail<NACC>(a, slope, a.out.p + (int64_t)mb * a.out.ld + cout_off + n, a.out.ld,
+                            a.res_mode ? a.res.p + (int64_t)mb * a.res.ld + cout_off + n : nullptr, a.res.ld, val, ok, eo);
     }
 }
 

@@ -198,23 +198,15 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_patch(ConvArgs a, int 
         const int64_t mb = ((int64_t)n * ho + oyb) * wo + oxb;
         float *ob = a.out.p + mb * ldo + cout_off;
         const float *rb = a.res_mode ? a.res.p + mb * ldr + cout_off : nullptr;
+        auto ok = [&](int r) { const int rl = (r & 3) + 8 * (r >> 2); return oyb + rl / TW < ho && oxb + rl % TW < wo; };
+        auto eo = [&](int r) { const int rl = (r & 3) + 8 * (r >> 2); return (int64_t)(rl / TW) * wo + rl % TW; };
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rl = (r & 3) + 8 * (r >> 2), dy = rl / TW, dx = rl % TW;
-            if (oyb + dy >= ho || oxb + dx >= wo) continue;
-            const int64_t eo = (int64_t)dy * wo + dx, m = mb + eo;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nn = ncol[j];
-                if (nn >= a.cout_g) continue;
-                float v = acc[i][j][r];
-                if constexpr (SER) v = tot[i][j][r] + v;
-                if (!SER && a.ksplit > 1) { a.partial[(m * a.ksplit + ks) * a.cout_g + nn] = v; continue; }
-                if (a.res_mode == 1) v += rb[eo * ldr + nn];
-                v = apply_act(v, a.act, slope[j]);
-                if (a.res_mode == 2) v += rb[eo * ldr + nn];
-                ob[eo * ldo + nn] = v;
-            }
+        for (int j = 0; j < TN; ++j) {
+            const int nn = ncol[j];
+            if (nn >= a.cout_g) continue;
+            auto val = [&](int r) { if constexpr (SER) return tot[i][j][r] + acc[i][j][r]; else return acc[i][j][r]; };
+            if (!SER && a.ksplit > 1) conv_tail_partial<16>(a.partial + (mb * a.ksplit + ks) * a.cout_g + nn, (int64_t)a.ksplit * a.cout_g, val, ok, eo);
+            else conv_tail<16>(a, slope[j], ob + nn, ldo, rb + nn, ldr, val, ok, eo);
         }
     }
 }
@@ -483,22 +475,14 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_patch_p(ConvArgs a,
             const int64_t mb = ((int64_t)n * ho + oyb) * wo + oxb;
             float *ob = a.out.p + mb * ldo + cout_off;
             const float *rb = a.res_mode ? a.res.p + mb * ldr + cout_off : nullptr;
+            auto ok = [&](int rr) { const int rl = (rr & 3) + 8 * (rr >> 2); return oyb + rl / TW < ho && oxb + rl % TW < wo; };
+            auto eo = [&](int rr) { const int rl = (rr & 3) + 8 * (rr >> 2); return (int64_t)(rl / TW) * wo + rl % TW; };
 #pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int rl = (rr & 3) + 8 * (rr >> 2), dy = rl / TW, dx = rl % TW;
-                if (oyb + dy >= ho || oxb + dx >= wo) continue;
-                const int64_t eo = (int64_t)dy * wo + dx;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int nn = ncol[j];
-                    if (nn >= a.cout_g) continue;
-                    float v = acc[i][j][rr];
-                    if constexpr (SER) v = tot[i][j][rr] + v;
-                    if (a.res_mode == 1) v += rb[eo * ldr + nn];
-                    v = apply_act(v, a.act, slope[j]);
-                    if (a.res_mode == 2) v += rb[eo * ldr + nn];
-                    ob[eo * ldo + nn] = v;
-                }
+            for (int j = 0; j < TN; ++j) {
+                const int nn = ncol[j];
+                if (nn >= a.cout_g) continue;
+                conv_tail<16>(a, slope[j], ob + nn, ldo, rb + nn, ldr,
+                              [&](int rr) { if constexpr (SER) return tot[i][j][rr] + acc[i][j][rr]; else return acc[i][j][rr]; }, ok, eo);
             }
         }
     }
@@ -658,21 +642,13 @@ __global__ __launch_bounds__(512, 2) void k_conv_ws(ConvArgs a, int tiles_x, int
         const int64_t mb = ((int64_t)n * ho + oyb) * wo + oxb;
         float *ob = a.out.p + mb * ldo + cout_off;
         const float *rb = a.res_mode ? a.res.p + mb * ldr + cout_off : nullptr;
+        auto ok = [&](int rr) { const int rl = (rr & 3) + 8 * (rr >> 2); return oyb + rl / TW < ho && oxb + rl % TW < wo; };
+        auto eo = [&](int rr) { const int rl = (rr & 3) + 8 * (rr >> 2); return (int64_t)(rl / TW) * wo + rl % TW; };
 #pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-            const int rl = (rr & 3) + 8 * (rr >> 2), dy = rl / TW, dx = rl % TW;
-            if (oyb + dy >= ho || oxb + dx >= wo) continue;
-            const int64_t eo = (int64_t)dy * wo + dx;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nn = ncol[j];
-                if (nn >= a.cout_g) continue;
-                float v = acc[j][rr];
-                if (a.res_mode == 1) v += rb[eo * ldr + nn];
-                v = apply_act(v, a.act, slope[j]);
-                if (a.res_mode == 2) v += rb[eo * ldr + nn];
-                ob[eo * ldo + nn] = v;
-            }
+        for (int j = 0; j < TN; ++j) {
+            const int nn = ncol[j];
+            if (nn >= a.cout_g) continue;
+            conv_tail<16>(a, slope[j], ob + nn, ldo, rb + nn, ldr, [&](int rr) { return acc[j][rr]; }, ok, eo);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the trailing (dead) fetches must land before the block's LDS is released

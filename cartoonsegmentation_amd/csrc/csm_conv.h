@@ -118,6 +118,55 @@ struct ConvArgs {
     unsigned dv_hw_mul, dv_hw_shr, dv_w_mul, dv_w_shr;   // magic numbers of m / (ho * wo) and rem / wo (fast_div; filled by set_fast_div)
 };
 
+// ---- shared tail of the direct conv kernels: the N values of ONE accumulator that a lane holds (same output channel, N pixels) ----------
+//   val(r): the finished sum of element r;  ok(r): element r lies inside the output;  eo(r): its pixel offset from the lane's first one,
+//   so that the element is ob[eo(r) * ldo] and its residual value rb[eo(r) * ldr].
+// Order: ALL residual loads of the accumulator first (range-guarded, N independent loads in flight), then the arithmetic, then the
+// stores.  With the load next to its store every element was a round trip of its own -- load, wait, store: the store may alias the next
+// load, so the compiler keeps the order, and the wait for a load also drains the stores issued before it.  A lane reads exactly the
+// elements it writes, so a residual view that IS the output view gives the same result as before (include/csm355.h: any other overlap
+// of the two is not allowed).  The block-uniform decisions are taken outside the element loop: the activation is a template argument
+// (-1 = the run-time switch of apply_act for the rare ones) and the two residual modes are selects on a uniform flag, not branches.
+// The arithmetic per element is unchanged: v + bias is in val(r); res_mode 1 add, activation, res_mode 2 add.
+template <int ACT, int N, class Val, class Ok, class Eo>
+__device__ __forceinline__ void conv_tail_act(const ConvArgs &a, float slope, float *ob, int64_t ldo, const float (&rv)[N], Val &&val, Ok &&ok, Eo &&eo) {
+    const bool pre = a.res_mode == 1, post = a.res_mode == 2;
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+        if (!ok(r)) continue;
+        float v = val(r);
+        const float vr = v + rv[r];
+        v = pre ? vr : v;
+        v = apply_act(v, ACT >= 0 ? ACT : a.act, slope);
+        const float vp = v + rv[r];
+        ob[eo(r) * ldo] = post ? vp : v;
+    }
+}
+template <int N, class Val, class Ok, class Eo>
+__device__ __forceinline__ void conv_tail(const ConvArgs &a, float slope, float *ob, int64_t ldo, const float *rb, int64_t ldr, Val &&val, Ok &&ok, Eo &&eo) {
+    float rv[N];
+#pragma unroll
+    for (int r = 0; r < N; ++r) rv[r] = 0.0f;
+    if (a.res_mode) {
+#pragma unroll
+        for (int r = 0; r < N; ++r)
+            if (ok(r)) rv[r] = rb[eo(r) * ldr];
+    }
+    switch (a.act) {                                           // uniform: the common activations get a body without the per-element switch
+        case CSM_ACT_NONE: conv_tail_act<CSM_ACT_NONE, N>(a, slope, ob, ldo, rv, val, ok, eo); break;
+        case CSM_ACT_RELU: conv_tail_act<CSM_ACT_RELU, N>(a, slope, ob, ldo, rv, val, ok, eo); break;
+        case CSM_ACT_SILU: conv_tail_act<CSM_ACT_SILU, N>(a, slope, ob, ldo, rv, val, ok, eo); break;
+        default: conv_tail_act<-1, N>(a, slope, ob, ldo, rv, val, ok, eo); break;
+    }
+}
+// the parallel split-K form of the same accumulator: raw sums into the partial buffer, element r at pb[eo(r) * ldp]
+template <int N, class Val, class Ok, class Eo>
+__device__ __forceinline__ void conv_tail_partial(float *pb, int64_t ldp, Val &&val, Ok &&ok, Eo &&eo) {
+#pragma unroll
+    for (int r = 0; r < N; ++r)
+        if (ok(r)) pb[eo(r) * ldp] = val(r);
+}
+
 // Row set-up of the LDS-DMA loaders: output row m -> (sample, oy, ox) with two divisions by run-time constants, and the validity mask of
 // its kh x kw taps.  The compiler's 32-bit division is ~35 vector instructions and the tap double loop ~9 per tap; on short-K tiles (K = 288:
 // 144 MFMAs per wave) the loader's set-up was a third of the 1 337 vector instructions a wave executes (profiles/r04_grouped_conv_pmc.txt).

@@ -182,8 +182,25 @@ __global__ __launch_bounds__(256, 3) void k_conv_grouped(ConvArgs a, int tx_n, i
         float sl[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) sl[t] = (a.act == CSM_ACT_PRELU && a.slope) ? a.slope[co0 + t] : 0.0f;
+        // the residual values of pixel j + 1 are requested BEFORE pixel j is stored (a load behind a store that may alias it waits for
+        // the store: one round trip per pixel otherwise)
+        auto load_res = [&](int j, float (&rr)[8]) {
+            const int ox = tx * TW + q + 8 * j;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) rr[t] = 0.0f;
+            if (!a.res_mode || j >= PX || oy >= a.out.h || ox >= a.out.w) return;
+            const float *rp = a.res.p + (((int64_t)n * a.out.h + oy) * a.out.w + ox) * a.res.ld + co0;
+            const f32x4g r0 = *reinterpret_cast<const f32x4g *>(rp), r1 = *reinterpret_cast<const f32x4g *>(rp + 4);
+            rr[0] = r0.x; rr[1] = r0.y; rr[2] = r0.z; rr[3] = r0.w; rr[4] = r1.x; rr[5] = r1.y; rr[6] = r1.z; rr[7] = r1.w;
+        };
+        float rnext[8];
+        load_res(0, rnext);
 #pragma nounroll
         for (int j = 0; j < PX; ++j) {
+            float rv[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) rv[t] = rnext[t];
+            load_res(j + 1, rnext);
             f32x2g s[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
@@ -194,11 +211,7 @@ __global__ __launch_bounds__(256, 3) void k_conv_grouped(ConvArgs a, int tx_n, i
             const int ox = tx * TW + q + 8 * j;
             if (oy >= a.out.h || ox >= a.out.w) continue;
             const int64_t m = ((int64_t)n * a.out.h + oy) * a.out.w + ox;
-            float v[8] = {s[0].x, s[0].y, s[1].x, s[1].y, s[2].x, s[2].y, s[3].x, s[3].y}, rv[8] = {};
-            if (a.res_mode) {
-                const f32x4g r0 = *reinterpret_cast<const f32x4g *>(a.res.p + m * a.res.ld + co0), r1 = *reinterpret_cast<const f32x4g *>(a.res.p + m * a.res.ld + co0 + 4);
-                rv[0] = r0.x; rv[1] = r0.y; rv[2] = r0.z; rv[3] = r0.w; rv[4] = r1.x; rv[5] = r1.y; rv[6] = r1.z; rv[7] = r1.w;
-            }
+            float v[8] = {s[0].x, s[0].y, s[1].x, s[1].y, s[2].x, s[2].y, s[3].x, s[3].y};
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 float x = v[t];

@@ -82,6 +82,16 @@ template <int VM> __device__ __forceinline__ void wait_barrier() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(VM) : "memory");
 }
 
+// barrier of the epilogue's exchange rounds: LDS traffic only (nothing is fetched INTO LDS there any more)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Fused epilogue, residual layers: rounds whose residual values are requested in front of the FIRST exchange barrier (2 = both, 48 loads in
+// flight per lane; 1 = each round in front of its own barrier, where the wait for round 1's values also drains round 0's stores).
+// -DCSM_WINO4_RES_AHEAD=1 builds the other depth for a measurement (profiles/residual_epilogue_after.txt)
+#ifndef CSM_WINO4_RES_AHEAD
+#define CSM_WINO4_RES_AHEAD 2
+#endif
+constexpr int kResAhead = CSM_WINO4_RES_AHEAD;
+
 // packed fp32 on the transform's channel pairs: v_pk_fma_f32 / v_pk_add_f32 are the same IEEE operations per component at half the VALU
 // issue (the compiler splits __builtin_elementwise_fma back into two v_fma_f32 here, hence the asm).  The coefficient is a wave-uniform
 // scalar: an SGPR pair whose LOW half feeds both components (op_sel_hi:[0,1,1])
@@ -151,8 +161,8 @@ static_assert(kPS == 18 && lds_all_of(6) <= 160u * 1024u, "tile shape");
 // Pixel entry of patch position (R, C) of a square: psi = R * 19 + colpos(C), colpos = the columns de-interleaved by C mod 4 (0..4 | 5..9 |
 // 10..13 | 14..17), so that the stride-4 windows of a tile row are consecutive entries.  psi_k(r, c): the compile-time part for window
 // position (r, c) of tile (ty, tx): psi = 19 (4 ty + r) + colbase(c & 3) + tx + (c >> 2).
-__host__ __device__ constexpr int colbase(int cr) { return cr == 0 ? 0 : (cr == 1 ? 5 : (cr == 2 ? 10 : 14)); }
-__host__ __device__ constexpr int psi_k(int r, int c) { return r * kPitch + colbase(c & 3) + (c >> 2); }
+__host__ __device__ __forceinline__ constexpr int colbase(int cr) { return cr == 0 ? 0 : (cr == 1 ? 5 : (cr == 2 ? 10 : 14)); }
+__host__ __device__ __forceinline__ constexpr int psi_k(int r, int c) { return r * kPitch + colbase(c & 3) + (c >> 2); }
 
 // ABL (development ablations, timing only -- results invalid): 1 = no DMA, 2 = no transform, 4 = no MFMA, 8 = no epilogue stores,
 // 16 = no barrier in the main loop, 32 = no operand reads (A / B fragments) in the main loop, 64 = every block stores into the first
@@ -453,25 +463,46 @@ __global__ __launch_bounds__(128 * RPB, RPB == 1 ? 1 : (RPB == 6 ? 3 : 2)) void 
     };
     // exchange area of a round: [wave][element pair p of the round's four][b][lane][2] (8 KB per wave).  A unit of the row pass = (pair p,
     // output column b): six ds_read_b64, one packed O6 over the frequency rows, eight outputs (two tiles x four output rows a).
-    // ACT: compile-time activation (-1 = the run-time switch of apply_act); FULL: interior block; RES: a residual is added
-    auto finish = [&](auto ACT, auto FULL, auto RES, int h, int u) __attribute__((always_inline)) {
+    // ACT: compile-time activation (-1 = the run-time switch of apply_act); FULL: interior block; RES: a residual is added (its eight
+    // values are in `rv`, fetched by fetch_res long before)
+    // pixel of element 0 of unit u of round h (elements r0 = 8 h + 2 pr and r0 + 1: square h, tile row 2 ((r0 >> 2) & 1) + lh, tile
+    // columns (r0 & 3) + e): the one place the residual fetch and the stores take their addresses from
+    auto unit_pixel = [&](int h, int u, int &oyb, int &oxb) __attribute__((always_inline)) {
+        const int pr = u >> 2, b = u & 3, r0 = 8 * h + 2 * pr;
+        oyb = (h ? sqy[1] : sqy[0]) + 4 * (2 * ((r0 >> 2) & 1) + le_h);
+        oxb = (h ? sqx[1] : sqx[0]) + 4 * (r0 & 3) + b;
+    };
+    // The residual values of a unit, element E at the pixel the unit's store E writes.  A unit past the round's sixteen (waves 4 and 5 own
+    // two, not three) gets a descriptor without records like an empty square: its loads are dropped, and the fetch stays branch-free
+    // (`is_full` is a run-time flag here: one body -- two bodies behind a branch load into the same registers, and the second waits
+    // for the first)
+    auto fetch_res = [&](bool is_full, int h, int u, float (&rv)[8]) __attribute__((always_inline)) {
+        const int sn = h ? sqn[1] : sqn[0];
+        const bool live = (h ? sqv[1] : sqv[0]) && u < 16;
+        const __amdgpu_buffer_rsrc_t rr_ = __builtin_amdgcn_make_buffer_rsrc(a.res.p + (int64_t)sn * ho * wo * ldr, 0,
+                                                                              live ? (int)((((int64_t)ho * wo - 1) * ldr + a.res.c) * 4) : 0, 0x00020000);
+        int oyb, oxb;
+        unit_pixel(h, u & 15, oyb, oxb);
+        const unsigned vbr = ((unsigned)(oyb * wo + oxb) * (unsigned)ldr + (unsigned)co) * 4u;
+        static_for<8>([&](auto E) {
+            constexpr int e = decltype(E)::value & 1, aa = decltype(E)::value >> 1;
+            const bool ok = (int)is_full | ((int)(oyb + aa < ho) & (int)(oxb + 4 * e < wo));      // (no short circuit: straight-line code)
+            rv[decltype(E)::value] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr_, ok ? (int)vbr : (int)kOob, (aa * wo + 4 * e) * ldr * 4, 0));
+        });
+    };
+    auto finish = [&](auto ACT, auto FULL, auto RES, int h, int u, const float (&rv)[8]) __attribute__((always_inline)) {
         constexpr int act_c = decltype(ACT)::value;
         constexpr bool has_res = decltype(RES)::value, is_full = decltype(FULL)::value;
-        const int pr = u >> 2, b = u & 3;
         f32x2n S[6], Y[4];
 #pragma unroll
         for (int i = 0; i < 6; ++i) S[i] = lds_read2(xr + (unsigned)i * 8192u + (unsigned)u * 512u);
-        // elements r0 = 8 h + 2 pr and r0 + 1: square h, tile row 2 ((r0 >> 2) & 1) + lh, tile columns (r0 & 3) + e
-        const int r0 = 8 * h + 2 * pr, sn = h ? sqn[1] : sqn[0], sy = h ? sqy[1] : sqy[0], sx = h ? sqx[1] : sqx[0];
+        const int sn = h ? sqn[1] : sqn[0];
         const bool sv = h ? sqv[1] : sqv[0];
         const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(a.out.p + (int64_t)sn * ho * wo * ldo, 0,
                                                                              sv ? (int)((((int64_t)ho * wo - 1) * ldo + a.out.c) * 4) : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rr_ = __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p + (int64_t)sn * ho * wo * ldr : a.out.p, 0,
-                                                                              (has_res && sv) ? (int)((((int64_t)ho * wo - 1) * ldr + a.res.c) * 4) : 0, 0x00020000);
-        const int oyb = sy + 4 * (2 * ((r0 >> 2) & 1) + le_h), oxb = sx + 4 * (r0 & 3) + b;
-        const unsigned pix = (unsigned)(oyb * wo + oxb);
-        unsigned vb = (pix * (unsigned)ldo + (unsigned)co) * 4u;
-        const unsigned vbr = (pix * (unsigned)ldr + (unsigned)co) * 4u;
+        int oyb, oxb;
+        unit_pixel(h, u, oyb, oxb);
+        unsigned vb = ((unsigned)(oyb * wo + oxb) * (unsigned)ldo + (unsigned)co) * 4u;
         if constexpr (ABL & 64) vb &= 0x3ffffu;
         at6p(S[0], S[1], S[2], S[3], S[4], S[5], Y);
         static_for<8>([&](auto E) {
@@ -480,20 +511,20 @@ __global__ __launch_bounds__(128 * RPB, RPB == 1 ? 1 : (RPB == 6 ? 3 : 2)) void 
             const bool ok = is_full || (oyb + aa < ho && oxb + 4 * e < wo);      // (an empty square's descriptor has no records: everything is dropped)
             const int so = (ABL & 64) ? 0 : (aa * wo + 4 * e) * ldo * 4;
             if constexpr (has_res) {
-                const float rv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr_, ok ? (int)vbr : (int)kOob, (aa * wo + 4 * e) * ldr * 4, 0));
-                if (a.res_mode == 1) v += rv;
+                const float r = rv[decltype(E)::value];
+                if (a.res_mode == 1) v += r;
                 v = apply_act(v, act_c >= 0 ? act_c : a.act, slope);
-                if (a.res_mode == 2) v += rv;
+                if (a.res_mode == 2) v += r;
             } else v = apply_act(v, act_c >= 0 ? act_c : a.act, slope);
             if constexpr (!(ABL & 8)) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, ok ? (int)vb : (int)kOob, so, 0);
         });
     };
-    auto finish_act = [&](auto FULL, auto RES, int h, int u) __attribute__((always_inline)) {
+    auto finish_act = [&](auto FULL, auto RES, int h, int u, const float (&rv)[8]) __attribute__((always_inline)) {
         switch (a.act) {                                       // uniform: the common activations get a body without the per-element switch
-            case CSM_ACT_NONE: finish(ic<CSM_ACT_NONE>{}, FULL, RES, h, u); break;
-            case CSM_ACT_RELU: finish(ic<CSM_ACT_RELU>{}, FULL, RES, h, u); break;
-            case CSM_ACT_SILU: finish(ic<CSM_ACT_SILU>{}, FULL, RES, h, u); break;
-            default: finish(ic<-1>{}, FULL, RES, h, u); break;
+            case CSM_ACT_NONE: finish(ic<CSM_ACT_NONE>{}, FULL, RES, h, u, rv); break;
+            case CSM_ACT_RELU: finish(ic<CSM_ACT_RELU>{}, FULL, RES, h, u, rv); break;
+            case CSM_ACT_SILU: finish(ic<CSM_ACT_SILU>{}, FULL, RES, h, u, rv); break;
+            default: finish(ic<-1>{}, FULL, RES, h, u, rv); break;
         }
     };
     // column pass (over j) of this wave's frequency row for all 16 accumulator elements FIRST (the 32x32 accumulators are register tuples:
@@ -510,6 +541,27 @@ __global__ __launch_bounds__(128 * RPB, RPB == 1 ? 1 : (RPB == 6 ? 3 : 2)) void 
             for (int b = 0; b < 4; ++b) lds_write2(xw + (unsigned)(decltype(PP)::value * 4 + b) * 512u, sv[decltype(PP)::value][b]);
         }
     });
+    // Residual layers: the values this wave adds -- units wi + 6 k of round h, [h][k][element] -- are ALL requested here, behind the
+    // column pass (the 96 accumulator registers are free now) and in front of the first exchange barrier: 48 independent loads in flight
+    // per lane, waited for with counted waits where a unit uses them.  Loading an element next to its store instead made every element
+    // a round trip of its own (load, wait, store; the store may alias the next load, so the compiler kept the order, and a wait for
+    // a load also drains the stores before it): ~43 dependent trips per lane in a kernel that has its CU to itself.  A lane reads exactly
+    // the elements it writes later, so a residual view that IS the output view stays correct (include/csm355.h).
+    float rv[2][3][8];
+    auto square_full = [&](int h) { return (h ? sqy[1] : sqy[0]) + kSQ <= ho && (h ? sqx[1] : sqx[0]) + kSQ <= wo; };   // an interior square skips the per-pixel range tests
+    auto fetch_round = [&](auto H) __attribute__((always_inline)) {
+        constexpr int h = decltype(H)::value;
+        static_for<3>([&](auto K) {
+            constexpr int k = decltype(K)::value;
+            fetch_res(square_full(h), h, wi + 6 * k, rv[h][k]);
+        });
+    };
+    __builtin_amdgcn_sched_barrier(0);                         // (not above the column pass: its registers are still taken there)
+    if (a.res_mode) {
+        fetch_round(ic<0>{});
+        if constexpr (kResAhead >= 2) fetch_round(ic<1>{});
+    }
+    // (the barriers of the exchange wait for LDS traffic only: residual loads and output stores stay in flight across them)
     static_for<2>([&](auto H) {
         constexpr int h = decltype(H)::value;
         if constexpr (h == 1) {
@@ -517,16 +569,21 @@ __global__ __launch_bounds__(128 * RPB, RPB == 1 ? 1 : (RPB == 6 ? 3 : 2)) void 
 #pragma unroll
                 for (int b = 0; b < 4; ++b) lds_write2(xw + (unsigned)(decltype(PP)::value * 4 + b) * 512u, sv[4 + decltype(PP)::value][b]);
             });
+            if constexpr (kResAhead < 2) { if (a.res_mode) fetch_round(ic<1>{}); }
         }
-        wait_barrier<0>();
+        lds_barrier();
         // row pass (over i) + bias / residual / activation: this wave finishes units wi, wi + 6, wi + 12 (< 16) of the round
-        const bool full = (h ? sqy[1] : sqy[0]) + kSQ <= ho && (h ? sqx[1] : sqx[0]) + kSQ <= wo;     // an interior square skips the per-pixel range tests
+        const bool full = square_full(h);
         for (int u = wi; u < 16; u += 6) {
-            if (a.res_mode) { if (full) finish_act(std::true_type{}, std::true_type{}, h, u); else finish_act(std::false_type{}, std::true_type{}, h, u); }
-            else if (full) finish_act(std::true_type{}, std::false_type{}, h, u);
-            else finish_act(std::false_type{}, std::false_type{}, h, u);
+            if (a.res_mode) {
+                if (full) finish_act(std::true_type{}, std::true_type{}, h, u, rv[h][0]); else finish_act(std::false_type{}, std::true_type{}, h, u, rv[h][0]);
+                // the round's values are a queue: the next unit's move to the front (one body per activation, not one per unit)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { rv[h][0][e] = rv[h][1][e]; rv[h][1][e] = rv[h][2][e]; }
+            } else if (full) finish_act(std::true_type{}, std::false_type{}, h, u, rv[h][0]);
+            else finish_act(std::false_type{}, std::false_type{}, h, u, rv[h][0]);
         }
-        if constexpr (h == 0) wait_barrier<0>();              // the exchange area is rewritten by the second round
+        if constexpr (h == 0) lds_barrier();                  // the exchange area is rewritten by the second round
     });
 }
 
@@ -551,6 +608,15 @@ __global__ __launch_bounds__(256) void k_wino4_rowpass(ConvArgs a, int tx_n, int
     Y[3] = at6(S[0].w, S[1].w, S[2].w, S[3].w, S[4].w, S[5].w);
     const float bias = a.bias ? a.bias[co] : 0.0f, slope = a.slope ? a.slope[co] : 0.0f;
     const int ho = a.out.h, wo = a.out.w;
+    // the tile's residual values first (all sixteen in flight at once), then arithmetic and stores: a load next to its store is a round
+    // trip per element, because the store may alias the next load
+    float rv[16];
+    static_for<16>([&](auto E) {
+        constexpr int e = decltype(E)::value, dy = e >> 2, dx = e & 3;
+        const int oy = 4 * tyg + dy, ox = 4 * txg + dx;
+        rv[e] = 0.0f;
+        if (a.res_mode && oy < ho && ox < wo) rv[e] = a.res.p[(((int64_t)n * ho + oy) * wo + ox) * a.res.ld + co];
+    });
     static_for<16>([&](auto E) {
         constexpr int e = decltype(E)::value, dy = e >> 2, dx = e & 3;
         const int oy = 4 * tyg + dy, ox = 4 * txg + dx;
@@ -558,9 +624,9 @@ __global__ __launch_bounds__(256) void k_wino4_rowpass(ConvArgs a, int tx_n, int
             const int64_t m = ((int64_t)n * ho + oy) * wo + ox;
             const f32x4n yb = Y[dx];
             float v = (dy == 0 ? yb.x : (dy == 1 ? yb.y : (dy == 2 ? yb.z : yb.w))) + bias;
-            if (a.res_mode == 1) v += a.res.p[m * a.res.ld + co];
+            if (a.res_mode == 1) v += rv[e];
             v = apply_act(v, a.act, slope);
-            if (a.res_mode == 2) v += a.res.p[m * a.res.ld + co];
+            if (a.res_mode == 2) v += rv[e];
             a.out.p[m * a.out.ld + co] = v;
         }
     });

@@ -281,7 +281,10 @@ typedef struct csm_op {
     int32_t kh, kw, stride, pad, dil;
     int32_t groups;          /* CONV: number of super-groups (1 = dense); each maps cin_g -> cout_g channels */
     int32_t cin_g, cout_g;
-    int32_t act, res_mode;   /* res_mode: 0 none, 1 add before act, 2 add after act */
+    int32_t act, res_mode;   /* res_mode: 0 none, 1 add before act, 2 add after act.  CONV: the residual view (in1) may BE the output
+                                view (same buffer, same channel offset: an in-place add -- every kernel reads exactly the residual
+                                elements it writes, ahead of its stores); ANY OTHER overlap of the two views is not allowed: the
+                                residual values of a pixel are read before, after or while other blocks store theirs */
     int64_t w_off, b_off, aux_off;   /* float offsets into the weight buffer (aux = PReLU slopes); -1 = none */
     int32_t flags;           /* BILINEAR: bit 0 = align_corners.  CONV: bit 1 = stem (cin padded to 4): weights are packed with K =
                                 (tap, channel), 8 taps x 4 channels per 32-wide chunk, for k_conv_stem; the chain is unchanged.
