@@ -841,7 +841,8 @@ class KenBurnsPipeline:
             return [frames, objCommon]
 
 
-def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False, quality: int = 90, subsampling: str = '420'):
+def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False, quality: int = 90, subsampling: str = '420',
+                    method: int = 0):
     """kenburns_effect.py:1086-1090 (BGR->RGB, optional ping-pong, 25 fps mp4 through moviepy).
 
     A path ending in .avi (any letter case) is written as a Motion-JPEG AVI instead: the frames -- a list of BGR numpy frames,
@@ -857,8 +858,12 @@ def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False
     `quality` and `subsampling` do not apply.
 
     A path ending in .webp (any letter case) is written as an animated WebP the same way: every frame one VP8 key frame, coded on
-    the device (ops.webp_streams with `quality`), the container by video.write_webp; `subsampling` does not apply."""
+    the device (ops.webp_streams with `quality` and `method`: 1 adds B_PRED and probability updates, about half the bytes), the
+    container by video.write_webp; `subsampling` does not apply.  `method` applies to .webp alone."""
     suffix = str(video_save_path).lower()
+    if suffix.endswith('.webp'):
+        from . import webpcode
+        webpcode.check_method(method, "npyframes2video")           # before the frames are uploaded
     if suffix.endswith('.avi') or suffix.endswith('.apng') or suffix.endswith('.gif') or suffix.endswith('.webp'):
         from . import video
         if isinstance(npy_frame_list, torch.Tensor):
@@ -879,7 +884,7 @@ def npyframes2video(npy_frame_list, video_save_path: str, playback: bool = False
             video.write_gif(video_save_path, streams, W, H, palette, fps=25, order=order)
             return
         if suffix.endswith('.webp'):
-            streams, W, H = ops.webp_streams(frames, quality=quality)
+            streams, W, H = ops.webp_streams(frames, quality=quality, method=method)
             order = video.playback_order(len(streams)) if playback else None
             video.write_webp(video_save_path, streams, W, H, fps=25, order=order)
             return

@@ -1125,7 +1125,7 @@ def png_encode(images, bgr=True):
 WEBP_SCRATCH_BYTES = 512 << 20         # frames are coded in chunks whose scratch stays below this (one frame is always taken)
 
 
-def webp_streams(frames, quality=90):
+def webp_streams(frames, quality=90, method=0):
     """The VP8 key frame (contract DESIGN.md §4.12) of every frame of the device uint8 frames [n,H,W,3] (or one [H,W,3]) in B, G, R
     order, one `bytes` per frame: returns (streams, width, height).  quality 1..100 picks the frame's one quantiser index.  Colour
     conversion, prediction, transforms and the boolean coder run on the device (csm_webp_measure / _write) in chunks of frames whose
@@ -1135,23 +1135,29 @@ def webp_streams(frames, quality=90):
     The format bounds what a frame may need, and only the coded sizes tell: the first partition (modes and skip flags, typically
     under 1 byte per macroblock, 6.2 at the very worst) must stay below 2^19 bytes and a token partition below 2^24.  Frames of
     1024 x 1024 at quality 90 stay below 1 % of either; a frame of several thousand pixels a side, or a very noisy one at a high
-    quality, can exceed it and then raises ValueError after the chunk's measure call, before any bytes are copied."""
+    quality, can exceed it and then raises ValueError after the chunk's measure call, before any bytes are copied.
+
+    method 0 (the default) writes 16x16 luma prediction and the default coefficient probabilities.  method 1 (contract DESIGN.md
+    §4.12b) adds B_PRED macroblocks -- ten 4x4 predictors, chosen against the 16x16 mode by an integer rate-distortion rule -- and
+    per-frame probability updates: files about half the size at the same quality number, for more device time per frame (§4.12b
+    has both measured).  A first partition of method 1 is larger (up to 103 bytes per macroblock at the very worst)."""
     from . import webpcode
     quality = webpcode.check_quality(quality, "webp_streams")
+    method = webpcode.check_method(method, "webp_streams")
     # named: alive until the kernels that read it are enqueued
     fr = _bgr_frames(frames, "webp_streams", lambda H, W: webpcode.check_size(W, H, "webp_streams"))
     n, H, W = (int(v) for v in fr.shape[:3])
     L, dev, st = _lib.load(), fr.device, stream_ptr(fr.device)
-    q, units = i32(quality), webpcode.partitions(H) + 1
-    per_frame = L.csm_webp_scratch_bytes(i32(1), i32(H), i32(W))
+    q, units, me = i32(quality), webpcode.partitions(H) + 1, i32(method)
+    per_frame = L.csm_webp_scratch_bytes_m(i32(1), i32(H), i32(W), me)
     step = max(1, min(WEBP_SCRATCH_BYTES // per_frame, (2 ** 20 - 1) // units))
     out = []
     for f0 in range(0, n, step):
         part = fr[f0:f0 + step]
         k = int(part.shape[0])
         info = torch.empty((k * units + 1, 2), dtype=torch.int64, device=dev)
-        scratch = torch.empty(L.csm_webp_scratch_bytes(i32(k), i32(H), i32(W)), dtype=torch.uint8, device=dev)
-        check(L.csm_webp_measure(ptr(part), i32(k), i32(H), i32(W), q, ptr(info), ptr(scratch), st), "webp_measure")
+        scratch = torch.empty(L.csm_webp_scratch_bytes_m(i32(k), i32(H), i32(W), me), dtype=torch.uint8, device=dev)
+        check(L.csm_webp_measure_m(ptr(part), i32(k), i32(H), i32(W), q, me, ptr(info), ptr(scratch), st), "webp_measure")
         info_h = info.cpu().numpy()                         # the one sync before the blob is sized
         status, total = int(info_h[-1, 0]), int(info_h[-1, 1])
         if status:
@@ -1162,18 +1168,18 @@ def webp_streams(frames, quality=90):
                              "partition of %d (limit %d)" % (W, H, quality, int(sizes[:, 0].max()), webpcode.MAX_FIRST_BYTES - 1,
                                                              int(sizes[:, 1:].max()), webpcode.MAX_PART_BYTES - 1))
         blob = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        check(L.csm_webp_write(i32(k), i32(H), i32(W), ptr(blob), i64(total), ptr(scratch), st), "webp_write")
+        check(L.csm_webp_write_m(i32(k), i32(H), i32(W), me, ptr(blob), i64(total), ptr(scratch), st), "webp_write")
         host = blob.cpu().numpy().tobytes()
         pieces = [host[o:o + b] for o, b in info_h[:-1].tolist()]
         out += [webpcode.vp8_frame(pieces[j * units], pieces[j * units + 1:(j + 1) * units], W, H) for j in range(k)]
     return out, W, H
 
 
-def webp_encode(frames, quality=90):
-    """Still WebP files (lossy, one VP8 key frame each; contract DESIGN.md §4.12) of device uint8 frames [n,H,W,3] (or one [H,W,3])
-    in B, G, R order: a list of n `bytes`, each a complete .webp file (webp_streams, then webpcode.still_file)."""
+def webp_encode(frames, quality=90, method=0):
+    """Still WebP files (lossy, one VP8 key frame each; contract DESIGN.md §4.12, method 1 §4.12b) of device uint8 frames [n,H,W,3]
+    (or one [H,W,3]) in B, G, R order: a list of n `bytes`, each a complete .webp file (webp_streams, then webpcode.still_file)."""
     from . import webpcode
-    return [webpcode.still_file(s) for s in webp_streams(frames, quality=quality)[0]]
+    return [webpcode.still_file(s) for s in webp_streams(frames, quality=quality, method=method)[0]]
 
 
 # ---- lossless WebP of device images (csrc/webpll.hip + webpcode.py; the instance cut-outs, utils.io_utils.imwrite) ------------

@@ -25,6 +25,14 @@ def check_quality(quality, what="webp"):
     return int(quality)
 
 
+def check_method(method, what="webp"):
+    """the lossy writer's coding method: the integer 0 (16x16 prediction, default probabilities) or 1 (B_PRED and
+    probability updates; §4.12b)"""
+    if isinstance(method, bool) or not isinstance(method, numbers.Integral) or method not in (0, 1):
+        raise ValueError("%s: method must be the integer 0 or 1 (got %r)" % (what, method))
+    return int(method)
+
+
 def quality_to_qi(quality):
     """the frame's one quantiser index: quality 100..1 onto 0..127, ((100 - quality) * 127 + 49) // 99"""
     return ((100 - int(quality)) * 127 + 49) // 99

@@ -754,6 +754,19 @@ size_t csm_webp_scratch_bytes(int n, int H, int W);
 int csm_webp_stage(int stage, const uint8_t *frames, int n, int H, int W, int quality, int64_t *info, void *scratch, void *stream);
 int csm_webp_measure(const uint8_t *frames, int n, int H, int W, int quality, int64_t *info, void *scratch, void *stream);
 int csm_webp_write(int n, int H, int W, uint8_t *out, int64_t out_bytes, void *scratch, void *stream);
+/* The same four calls with the coding method (contract DESIGN.md §4.12b, restated in tests/webp_m1_restatement.py, byte-identical).
+ * method 0 is the calls above, the same kernels and the same bytes.  method 1 adds B_PRED macroblocks (ten 4x4 predictors by SSE,
+ * 16x16 against B_PRED by an integer rate-distortion rule) and per-frame coefficient-probability updates: the macroblock pass walks
+ * diagonals of slope two, stage 3 counts the frame's branch decisions (k_webp_stats), derives its probabilities (k_webp_probs) and
+ * codes with them.  Any other method is CSM_ERR_ARG (scratch bytes 0).  The scratch of method 1 is larger: per macroblock 17 B of
+ * sub-block modes and carried Y2 contexts, per frame 10.6 KB of counters and tables, and a first partition sized for 1056 updates
+ * of 9 pairs and 117 pairs per macroblock; size it with csm_webp_scratch_bytes_m and pass the same method to every call of a chunk.
+ * info, the status word and the guarded stores are those of method 0; still one host read of info per chunk. */
+size_t csm_webp_scratch_bytes_m(int n, int H, int W, int method);
+int csm_webp_stage_m(int stage, const uint8_t *frames, int n, int H, int W, int quality, int method, int64_t *info, void *scratch,
+                     void *stream);
+int csm_webp_measure_m(const uint8_t *frames, int n, int H, int W, int quality, int method, int64_t *info, void *scratch, void *stream);
+int csm_webp_write_m(int n, int H, int W, int method, uint8_t *out, int64_t out_bytes, void *scratch, void *stream);
 
 /* The VP8L payload of a lossless WebP file for n images of any sizes (webpll.hip; contract DESIGN.md §4.13, restated in
  * tests/webpll_restatement.py, byte-identical).  One descriptor per image, int64 [n][csm_webpll_desc_words() = 8]: [0] the device
