@@ -1,6 +1,7 @@
 // conv_dma.hip -- k_conv_dma and its persistent form k_conv_dma_p: the implicit-GEMM convolution whose operand tiles go global -> LDS by
 // buffer_load ... lds (the main kernel of the dense nets), with their launchers and the mixed-tile launch.
 #include "csm_convcfg.h"
+#include "csm_convtile.h"
 
 using namespace csmconv;
 
@@ -27,7 +28,6 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma(ConvArgs a) {
     constexpr int GA = BM / 8 / NW, GB = BN / 8 / NW;          // DMA pieces (8 rows) per wave per chunk
     static_assert(GA * 8 * NW == BM && GB * 8 * NW == BN, "tile rows must split evenly over the waves");
     constexpr int kStageF = (BM + BN) * 32;                     // floats per stage
-    constexpr unsigned kOob = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -38,20 +38,13 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma(ConvArgs a) {
     block_to_tile(mt, ntile, zz, a.ngroup);
     const int m0 = a.m_begin + mt * BM, n0 = ntile * BN;
     const int g = SER ? zz : zz / a.ksplit, ks = SER ? 0 : zz - g * a.ksplit;
-    const int ho = a.out.h, wo = a.out.w;
     const int cin_off = g * a.cin_g, cout_off = g * a.cout_g;
     const int Tall = a.kh * a.kw * a.ncb;
     const int c_begin = SER ? 0 : (int)(((int64_t)ks * Tall) / a.ksplit), T = SER ? Tall : (int)(((int64_t)(ks + 1) * Tall) / a.ksplit);
 
     // buffer descriptors (raw, range-checked): activations view and this op's packed weights
     i32x4 ra, rb;
-    {
-        uint64_t pa = (uint64_t)a.in.p, pb = (uint64_t)a.w;
-        unsigned na = (unsigned)((((int64_t)a.in.n * a.in.h * a.in.w - 1) * a.in.ld + a.in.c) * 4);
-        unsigned nb = (unsigned)((int64_t)a.groups * Tall * a.npad * 128);
-        ra = i32x4{(int)(unsigned)pa, (int)(unsigned)(pa >> 32), (int)na, 0x00020000};
-        rb = i32x4{(int)(unsigned)pb, (int)(unsigned)(pb >> 32), (int)nb, 0x00020000};
-    }
+    conv_rsrc(a, Tall, ra, rb);
     // per-lane loader state.  A piece g: rows 8*(wave*GA+g)+lane/8 of the tile; physical slot lane%8 holds logical slot
     // (lane%8) ^ ((row>>1)&7).  offA = byte offset of (pixel's receptive-field origin, channel) -- may be "negative" (wraps)
     // for border pixels; a VALID tap always brings it back inside the view.
@@ -113,83 +106,26 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma(ConvArgs a) {
     // MFMA-side fragment addresses: row (32*tile + li), logical slot 2*kb + lh -> physical ^ ((li>>1)&7)
     int sw[4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) sw[kb] = ((2 * kb + lh) ^ ((li >> 1) & 7)) * 4;
+    for (int kb = 0; kb < 4; ++kb) sw[kb] = frag_slot(kb, li, lh);
     const int rowA = (32 * TM * wm + li) * 32, rowB = (BM + 32 * TN * wn + li) * 32;
-    f32x16 tot[SER ? TM : 1][SER ? TN : 1];
-    int run = 0, next_b = SER ? (int)((int64_t)Tall / a.ksplit) : 0;          // SER: first chunk of the next run
+    SerialRuns<SER, TM, TN> runs;
+    runs.begin(Tall, a.ksplit);
     auto compute = [&](int stage, int chunk) {
-        if constexpr (SER) {
-            if (chunk == next_b) {                                             // block-uniform: S - 1 times per block
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) { tot[i][j][r] = run == 0 ? acc[i][j][r] : tot[i][j][r] + acc[i][j][r]; acc[i][j][r] = 0.0f; }
-                ++run; next_b = (int)(((int64_t)(run + 1) * Tall) / a.ksplit);
-            }
-        }
+        runs.boundary(chunk, acc, Tall, a.ksplit);
         const float *S = lds + stage * kStageF;
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            float4 af[TM], bf[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const float4 *>(S + rowA + i * 1024 + sw[kb]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const float4 *>(S + rowB + j * 1024 + sw[kb]);
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const float av = t == 0 ? af[i].x : (t == 1 ? af[i].y : (t == 2 ? af[i].z : af[i].w));
-                        const float bv = t == 0 ? bf[j].x : (t == 1 ? bf[j].y : (t == 2 ? bf[j].z : bf[j].w));
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                    }
-        }
+        mfma_chunk(acc, [&](int kb, int i) { return *reinterpret_cast<const float4 *>(S + rowA + i * 1024 + sw[kb]); },
+                   [&](int kb, int j) { return *reinterpret_cast<const float4 *>(S + rowB + j * 1024 + sw[kb]); });
     };
 
     // ILV (two-stage pipeline): the DMA pieces of the next chunk go out BETWEEN the MFMA groups of this one instead of in a burst behind
     // the barrier (see k_conv_dma_p); branch-free -- behind the last chunk the lanes are out of range and the DMA writes zeros into the
     // stage nobody reads any more
     auto compute_ilv = [&](int stage, int fill, int chunk, bool live) {
-        if constexpr (SER) {
-            if (chunk == next_b) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) { tot[i][j][r] = run == 0 ? acc[i][j][r] : tot[i][j][r] + acc[i][j][r]; acc[i][j][r] = 0.0f; }
-                ++run; next_b = (int)(((int64_t)(run + 1) * Tall) / a.ksplit);
-            }
-        }
+        runs.boundary(chunk, acc, Tall, a.ksplit);
         const float *S = lds + stage * kStageF;
-        float4 af[2][TM], bf[2][TN];
-        auto rd = [&](int kb, int buf) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[buf][i] = *reinterpret_cast<const float4 *>(S + rowA + i * 1024 + sw[kb]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[buf][j] = *reinterpret_cast<const float4 *>(S + rowB + j * 1024 + sw[kb]);
-        };
-        rd(0, 0);
-        [&]<int... G>(std::integer_sequence<int, G...>) {
-            ([&] {
-                constexpr int kb = G / 4, t = G % 4, buf = kb & 1;
-                if constexpr (G < GA + GB) { piece(std::integral_constant<int, G>{}, fill, live); __builtin_amdgcn_sched_barrier(0); }
-                if constexpr (t == 1 && kb < 3) { rd(kb + 1, buf ^ 1); __builtin_amdgcn_sched_barrier(0); }
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const float av = t == 0 ? af[buf][i].x : (t == 1 ? af[buf][i].y : (t == 2 ? af[buf][i].z : af[buf][i].w));
-                        const float bv = t == 0 ? bf[buf][j].x : (t == 1 ? bf[buf][j].y : (t == 2 ? bf[buf][j].z : bf[buf][j].w));
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-            }(), ...);
-        }(std::make_integer_sequence<int, 16>{});
+        mfma_chunk_ilv<TM, TN, GA + GB>(acc, [&](int kb, int i) { return *reinterpret_cast<const float4 *>(S + rowA + i * 1024 + sw[kb]); },
+                                        [&](int kb, int j) { return *reinterpret_cast<const float4 *>(S + rowB + j * 1024 + sw[kb]); },
+                                        [&](auto G) { piece(G, fill, live); });
         advance();
     };
 
@@ -247,7 +183,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma(ConvArgs a) {
             const int mb = m0 + 32 * (TM * wm + i) + 4 * lh;
             float *ob = a.out.p + (int64_t)mb * ldo + cout_off + n;
             const float *rb = a.res_mode ? a.res.p + (int64_t)mb * ldr + cout_off + n : nullptr;
-            auto val = [&](int r) { if constexpr (SER) return tot[i][j][r] + acc[i][j][r]; else return acc[i][j][r]; };
+            auto val = [&](int r) { return runs.value(i, j, r, acc); };
             auto ok = [&](int r) { return mb + (r & 3) + 8 * (r >> 2) < a.M; };
             auto eo = [](int r) { return (int64_t)((r & 3) + 8 * (r >> 2)); };
             if (!SER && a.ksplit > 1) conv_tail_partial<16>(a.partial + ((int64_t)mb * a.ksplit + ks) * a.cout_g + n, (int64_t)a.ksplit * a.cout_g, val, ok, eo);
@@ -272,13 +208,11 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma_p(ConvArgs a, int n_n
     constexpr int GA = BM / 8 / NW, GB = BN / 8 / NW;
     static_assert(GA * 8 * NW == BM && GB * 8 * NW == BN, "tile rows must split evenly over the waves");
     constexpr int kStageF = (BM + BN) * 32;
-    constexpr unsigned kOob = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
-    const int ho = a.out.h, wo = a.out.w;
     const int Tall = a.kh * a.kw * a.ncb;
     // this block's tiles: XCD x = blockIdx & 7 owns the run [start, start + len) of the (z, m-tile, n-tile) order, n fastest
     const int per = (int)(gridDim.x >> 3), x = (int)(blockIdx.x & 7u), i0 = (int)(blockIdx.x >> 3);
@@ -288,13 +222,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma_p(ConvArgs a, int n_n
     const int per_z = a.m_tiles * n_n;
 
     i32x4 ra, rb;
-    {
-        uint64_t pa = (uint64_t)a.in.p, pb = (uint64_t)a.w;
-        unsigned na = (unsigned)((((int64_t)a.in.n * a.in.h * a.in.w - 1) * a.in.ld + a.in.c) * 4);
-        unsigned nb = (unsigned)((int64_t)a.groups * Tall * a.npad * 128);
-        ra = i32x4{(int)(unsigned)pa, (int)(unsigned)(pa >> 32), (int)na, 0x00020000};
-        rb = i32x4{(int)(unsigned)pb, (int)(unsigned)(pb >> 32), (int)nb, 0x00020000};
-    }
+    conv_rsrc(a, Tall, ra, rb);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float *)lds;
     const unsigned ldsA = lds0 + (unsigned)(wave * GA * 8) * 128u, ldsB = lds0 + (unsigned)(BM + wave * GB * 8) * 128u;
 
@@ -349,11 +277,10 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma_p(ConvArgs a, int n_n
 
     int sw[4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) sw[kb] = ((2 * kb + lh) ^ ((li >> 1) & 7)) * 4;
+    for (int kb = 0; kb < 4; ++kb) sw[kb] = frag_slot(kb, li, lh);
     const int rowA = (32 * TM * wm + li) * 32, rowB = (BM + 32 * TN * wn + li) * 32;
+    SerialRuns<SER, TM, TN> runs;                               // (reset per tile)
     f32x16 acc[TM][TN];
-    f32x16 tot[SER ? TM : 1][SER ? TN : 1];
-    int run = 0, next_b = 0;                                    // SER: first chunk of the next run (reset per tile)
     // ILV: the chunk's MFMAs with the DMA pieces of the NEXT chunk spread between them -- piece g goes out behind MFMA group g (a group =
     // one k step of all TM x TN accumulators), so the pieces leave in the first half of the chunk and the matrix pipe never waits for a
     // burst of GA + GB address computations and DMA issues behind the barrier (each costs the wave 60-180 cycles of issue time, which an
@@ -361,66 +288,15 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma_p(ConvArgs a, int n_n
     // sched_barrier: hipcc otherwise regroups the asm statements in front of the MFMAs.
     auto compute_ilv = [&](int stage, int fill) {
         const float *S = lds + stage * kStageF;
-        float4 af[2][TM], bf[2][TN];
-        auto rd = [&](int kb, int buf) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[buf][i] = *reinterpret_cast<const float4 *>(S + rowA + i * 1024 + sw[kb]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[buf][j] = *reinterpret_cast<const float4 *>(S + rowB + j * 1024 + sw[kb]);
-        };
-        rd(0, 0);
-        [&]<int... G>(std::integer_sequence<int, G...>) {
-            ([&] {
-                constexpr int kb = G / 4, t = G % 4, buf = kb & 1;
-                if constexpr (G < GA + GB) { piece(std::integral_constant<int, G>{}, fill); __builtin_amdgcn_sched_barrier(0); }
-                if constexpr (t == 1 && kb < 3) { rd(kb + 1, buf ^ 1); __builtin_amdgcn_sched_barrier(0); }
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const float av = t == 0 ? af[buf][i].x : (t == 1 ? af[buf][i].y : (t == 2 ? af[buf][i].z : af[buf][i].w));
-                        const float bv = t == 0 ? bf[buf][j].x : (t == 1 ? bf[buf][j].y : (t == 2 ? bf[buf][j].z : bf[buf][j].w));
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-            }(), ...);
-        }(std::make_integer_sequence<int, 16>{});
-        static_assert(GA + GB <= 16, "one DMA piece per MFMA group");
+        mfma_chunk_ilv<TM, TN, GA + GB>(acc, [&](int kb, int i) { return *reinterpret_cast<const float4 *>(S + rowA + i * 1024 + sw[kb]); },
+                                        [&](int kb, int j) { return *reinterpret_cast<const float4 *>(S + rowB + j * 1024 + sw[kb]); },
+                                        [&](auto G) { piece(G, fill); });
         advance();
-    };
-    auto run_boundary = [&](int chunk) {                        // block-uniform: S - 1 times per tile
-        if constexpr (SER) {
-            if (chunk == next_b) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int rr = 0; rr < 16; ++rr) { tot[i][j][rr] = run == 0 ? acc[i][j][rr] : tot[i][j][rr] + acc[i][j][rr]; acc[i][j][rr] = 0.0f; }
-                ++run; next_b = (int)(((int64_t)(run + 1) * Tall) / a.ksplit);
-            }
-        }
     };
     auto compute = [&](int stage) {
         const float *S = lds + stage * kStageF;
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            float4 af[TM], bf[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const float4 *>(S + rowA + i * 1024 + sw[kb]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const float4 *>(S + rowB + j * 1024 + sw[kb]);
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const float av = t == 0 ? af[i].x : (t == 1 ? af[i].y : (t == 2 ? af[i].z : af[i].w));
-                        const float bv = t == 0 ? bf[j].x : (t == 1 ? bf[j].y : (t == 2 ? bf[j].z : bf[j].w));
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                    }
-        }
+        mfma_chunk(acc, [&](int kb, int i) { return *reinterpret_cast<const float4 *>(S + rowA + i * 1024 + sw[kb]); },
+                   [&](int kb, int j) { return *reinterpret_cast<const float4 *>(S + rowB + j * 1024 + sw[kb]); });
     };
 
     loader_setup(i0, true);
@@ -441,14 +317,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma_p(ConvArgs a, int n_n
 #pragma unroll
                 for (int rr = 0; rr < 16; ++rr) acc[i][jj][rr] = b;
         }
-        if constexpr (SER) { run = 0; next_b = (int)((int64_t)Tall / a.ksplit); }
+        runs.begin(Tall, a.ksplit);
         for (int chunk = 0; chunk + 1 < Tall; ++chunk, st ^= 1) {
             // (lgkmcnt: this wave's fragment reads of the stage refilled next must have COMPLETED before it arrives -- hipcc may sink
             // the last MFMAs of the previous chunk, and with them the wait for their operands, below the barrier)
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            if constexpr (ILV) { run_boundary(chunk); compute_ilv(st, st ^ 1); }
-            else { issue(st ^ 1); run_boundary(chunk); compute(st); }
+            if constexpr (ILV) { runs.boundary(chunk, acc, Tall, a.ksplit); compute_ilv(st, st ^ 1); }
+            else { issue(st ^ 1); runs.boundary(chunk, acc, Tall, a.ksplit); compute(st); }
         }
         // the tile's last chunk: the NEXT tile's chunk 0 goes out behind the barrier (branch-free: past the end every lane is out
         // of range and the DMA writes zeros into a stage nobody reads)
@@ -460,7 +336,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma_p(ConvArgs a, int n_n
             loader_setup(more ? kn : k, more);
             if constexpr (!ILV) issue(st ^ 1);
         }
-        run_boundary(Tall - 1);
+        runs.boundary(Tall - 1, acc, Tall, a.ksplit);
         if constexpr (ILV) compute_ilv(st, st ^ 1); else compute(st);
         st ^= 1;
         // epilogue: lane holds column li of each 32x32 tile, rows (r&3) + 8*(r>>2) + 4*lh
@@ -476,7 +352,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_dma_p(ConvArgs a, int n_n
                 float *ob = a.out.p + (int64_t)mb * ldo + cout_off + n;
                 const float *rb = a.res_mode ? a.res.p + (int64_t)mb * ldr + cout_off + n : nullptr;
                 conv_tail<16>(a, slope, ob, ldo, rb, ldr,
-                              [&](int rr) { if constexpr (SER) return tot[i][jj][rr] + acc[i][jj][rr]; else return acc[i][jj][rr]; },
+                              [&](int rr) { return runs.value(i, jj, rr, acc); },
                               [&](int rr) { return mb + (rr & 3) + 8 * (rr >> 2) < a.M; }, [](int rr) { return (int64_t)((rr & 3) + 8 * (rr >> 2)); });
             }
         }

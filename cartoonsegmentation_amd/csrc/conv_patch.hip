@@ -1,6 +1,7 @@
 // conv_patch.hip -- the 3x3 (stride 1, dilation 1) convolutions that keep the input patch of a tile in LDS for all nine taps:
 // k_conv_patch, its persistent form k_conv_patch_p and the weights-stationary k_conv_ws, with their launchers.
 #include "csm_convcfg.h"
+#include "csm_convtile.h"
 
 using namespace csmconv;
 
@@ -36,7 +37,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_patch(ConvArgs a, int 
     constexpr int GB = BN / 8 / NW;
     static_assert(GB * 8 * NW == BN && TH * TW == BM && (TW == 16 || TW == 8), "tile shape");
     constexpr int kPatchF = QP * NW * 8 * 32, kBF = BN * 32;    // floats per patch stage (every wave's QP pieces have a home) / weight stage
-    constexpr unsigned kOob = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [patch 0][patch 1][B 0][B 1]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_patch(ConvArgs a, int 
     }
     int swb[4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) swb[kb] = ((2 * kb + lh) ^ ((li >> 1) & 7)) * 4;
+    for (int kb = 0; kb < 4; ++kb) swb[kb] = frag_slot(kb, li, lh);
     const int rowB = (32 * TN * wn + li) * 32;
     f32x16 tot[SER ? TM : 1][SER ? TN : 1];
     int run = 0, next_b = SER ? (int)((int64_t)Tall / a.ksplit) : 0;          // SER: first chunk of the next run
@@ -235,7 +235,6 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_patch_p(ConvArgs a,
     // last slice would let a weight DMA be in flight at the barrier
     static_assert(QP % kPPT == 0, "every patch slice must carry kPPT pieces (counted vmcnt)");
     constexpr int kPatchF = QP * NW * 8 * 32, kBF = BN * 32;
-    constexpr unsigned kOob = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [patch 0][patch 1][B 0][B 1]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -318,11 +317,10 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_patch_p(ConvArgs a,
     }
     int swb[4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) swb[kb] = ((2 * kb + lh) ^ ((li >> 1) & 7)) * 4;
+    for (int kb = 0; kb < 4; ++kb) swb[kb] = frag_slot(kb, li, lh);
     const int rowB = (32 * TN * wn + li) * 32;
+    SerialRuns<SER, TM, TN> runs;                               // (reset per tile)
     f32x16 acc[TM][TN];
-    f32x16 tot[SER ? TM : 1][SER ? TN : 1];
-    int run = 0, next_b = 0;                                    // SER: first chunk of the next run (reset per tile)
     auto compute = [&](int pstage, int tap, int bstage) {
         const float *SP = lds + pstage * kPatchF;
         const float *SB = lds + 2 * kPatchF + bstage * kBF;
@@ -330,24 +328,8 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_patch_p(ConvArgs a,
         int arow[TM], asw[TM];
 #pragma unroll
         for (int i = 0; i < TM; ++i) { int pp = ppb[i] + toff; arow[i] = pp * 32; asw[i] = patch_key<PW, TW>(pp); }
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            float4 af[TM], bf[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const float4 *>(SP + arow[i] + (((2 * kb + lh) ^ asw[i]) << 2));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const float4 *>(SB + rowB + j * 1024 + swb[kb]);
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const float av = t == 0 ? af[i].x : (t == 1 ? af[i].y : (t == 2 ? af[i].z : af[i].w));
-                        const float bv = t == 0 ? bf[j].x : (t == 1 ? bf[j].y : (t == 2 ? bf[j].z : bf[j].w));
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                    }
-        }
+        mfma_chunk(acc, [&](int kb, int i) { return *reinterpret_cast<const float4 *>(SP + arow[i] + (((2 * kb + lh) ^ asw[i]) << 2)); },
+                   [&](int kb, int j) { return *reinterpret_cast<const float4 *>(SB + rowB + j * 1024 + swb[kb]); });
     };
 
     patch_setup(i0, true);
@@ -370,7 +352,7 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_patch_p(ConvArgs a,
 #pragma unroll
                 for (int rr = 0; rr < 16; ++rr) acc[i][j][rr] = b;
         }
-        if constexpr (SER) { run = 0; next_b = (int)((int64_t)Tall / a.ksplit); }
+        runs.begin(Tall, a.ksplit);
         for (int cb = 0; cb < ncb; ++cb, ps ^= 1) {
             const bool last_cb = cb + 1 == ncb;
             // The next patch of the sequence -- block cb + 1 of this tile or (last block) block 0 of the NEXT tile, for which the loader
@@ -400,59 +382,29 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_patch_p(ConvArgs a,
                             dma16(offP[qq] == kOob ? kOob : offP[qq] + cbo, ra, psb + (unsigned)(wave + qq * NW) * 1024u);
                     }
                 }
-                if constexpr (SER) {
-                    if (9 * cb + tap == next_b) {                                  // block-uniform: S - 1 times per tile
-#pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                                for (int rr = 0; rr < 16; ++rr) { tot[i][j][rr] = run == 0 ? acc[i][j][rr] : tot[i][j][rr] + acc[i][j][rr]; acc[i][j][rr] = 0.0f; }
-                        ++run; next_b = (int)(((int64_t)(run + 1) * Tall) / a.ksplit);
-                    }
-                }
+                runs.boundary(9 * cb + tap, acc, Tall, a.ksplit);
                 if constexpr (!ILV) compute(ps, tap, st);
                 else {
                     // the tap's MFMAs with this tap's DMA pieces between the groups (same order as the burst: the weights of the next tap
                     // first, then the patch slice -- the counted vmcnt at the next barrier relies on it); see k_conv_dma_p
                     constexpr int NSL = tap < kPT ? ((tap + 1) * kPPT <= QP ? kPPT : QP - tap * kPPT) : 0;
-                    static_assert(GB + kPPT <= 16, "one DMA piece per MFMA group");
                     // fragment addresses = per-lane bases that do not depend on the tile (abase: 12 per accumulator row) + a tap constant + the
                     // stage: the nine unrolled taps used to keep 72 precomputed addresses per accumulator row alive (187 - 233 VGPRs)
                     constexpr int kh = tap / 3, kw = tap - 3 * kh, toff = kh * PW + kw;
                     const float *SP = lds + ps * kPatchF + toff * 32;
                     const float *SB = lds + 2 * kPatchF + st * kBF;
-                    float4 af[2][TM], bf[2][TN];
-                    auto rd = [&](int kb, int buf) {
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) af[buf][i] = *reinterpret_cast<const float4 *>(SP + abase[i][kw][kb]);
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) bf[buf][j] = *reinterpret_cast<const float4 *>(SB + rowB + j * 1024 + swb[kb]);
-                    };
-                    rd(0, 0);
-                    [&]<int... G>(std::integer_sequence<int, G...>) {
-                        ([&] {
-                            constexpr int kb = G / 4, t = G % 4, buf = kb & 1;
-                            if constexpr (G < GB) {
+                    mfma_chunk_ilv<TM, TN, GB + NSL>(
+                        acc, [&](int kb, int i) { return *reinterpret_cast<const float4 *>(SP + abase[i][kw][kb]); },
+                        [&](int kb, int j) { return *reinterpret_cast<const float4 *>(SB + rowB + j * 1024 + swb[kb]); },
+                        [&](auto GC) {
+                            constexpr int G = decltype(GC)::value;
+                            if constexpr (G < GB)
                                 dma16(offB[G] == kOob ? kOob : offB[G] + l_w, rb, ldsB + (unsigned)(st ^ 1) * (unsigned)(kBF * 4) + (unsigned)G * 1024u);
-                                __builtin_amdgcn_sched_barrier(0);
-                            } else if constexpr (G < GB + NSL) {
+                            else {
                                 constexpr int qq = tap * kPPT + (G - GB);
                                 dma16(offP[qq] == kOob ? kOob : offP[qq] + cbo, ra, psb + (unsigned)(wave + qq * NW) * 1024u);
-                                __builtin_amdgcn_sched_barrier(0);
                             }
-                            if constexpr (t == 1 && kb < 3) { rd(kb + 1, buf ^ 1); __builtin_amdgcn_sched_barrier(0); }
-#pragma unroll
-                            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                                for (int j = 0; j < TN; ++j) {
-                                    const float av = t == 0 ? af[buf][i].x : (t == 1 ? af[buf][i].y : (t == 2 ? af[buf][i].z : af[buf][i].w));
-                                    const float bv = t == 0 ? bf[buf][j].x : (t == 1 ? bf[buf][j].y : (t == 2 ? bf[buf][j].z : bf[buf][j].w));
-                                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                                }
-                            __builtin_amdgcn_sched_barrier(0);
-                        }(), ...);
-                    }(std::make_integer_sequence<int, 16>{});
+                        });
                     l_w += (unsigned)a.npad * 128u;
                 }
                 st ^= 1;
@@ -482,7 +434,7 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_patch_p(ConvArgs a,
                 const int nn = ncol[j];
                 if (nn >= a.cout_g) continue;
                 conv_tail<16>(a, slope[j], ob + nn, ldo, rb + nn, ldr,
-                              [&](int rr) { if constexpr (SER) return tot[i][j][rr] + acc[i][j][rr]; else return acc[i][j][rr]; }, ok, eo);
+                              [&](int rr) { return runs.value(i, j, rr, acc); }, ok, eo);
             }
         }
     }
@@ -505,7 +457,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_ws(ConvArgs a, int tiles_x, int
     constexpr int NW = 8, TW = 16, TH = 16, BN = 32 * TN;
     constexpr int PH = TH + 2, PW = TW + 2, NPIX = PH * PW, NPP = (NPIX + 7) / 8, QP = (NPP + NW - 1) / NW;
     constexpr int kPatchF = (NPP + 1) * 8 * 32;                 // floats per patch stage: NPP pieces + one dump slot for the surplus pieces of the last round
-    constexpr unsigned kOob = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [patch 0][patch 1][weight panel: chunk][BN rows][32]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
@@ -571,7 +522,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_ws(ConvArgs a, int tiles_x, int
     }
     int swb[4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) swb[kb] = li * 32 + ((2 * kb + lh) ^ ((li >> 1) & 7)) * 4;
+    for (int kb = 0; kb < 4; ++kb) swb[kb] = li * 32 + frag_slot(kb, li, lh);
     f32x16 acc[TN];
 
     patch_setup(i0, true);

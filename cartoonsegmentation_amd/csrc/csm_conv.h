@@ -1,6 +1,7 @@
-// csm_conv.h -- device / host helpers shared by the convolution translation units of libcsm355 (nets.hip, conv_*.hip, netops.hip,
-// wino.hip, wino4.hip, grouped.hip):
-// scalar math of the numerical contract, NHWC views, the conv argument block, XCD-aware tile order, LDS-DMA.
+// csm_conv.h -- device / host helpers shared by the convolution translation units of libcsm355 (nets.hip, conv_mfma.hip, conv_dma.hip,
+// conv_patch.hip, netops.hip, wino.hip, wino4.hip, grouped.hip; csm_convcfg.h and csm_convtile.h build on it):
+// scalar math of the numerical contract, NHWC views, the conv argument block, the shared tail of an accumulator (conv_tail), the row
+// set-up of the DMA loaders, XCD-aware tile order, LDS-DMA.  The pieces around the matrix pipe are in csm_convtile.h.
 #pragma once
 #include "csm_common.h"
 #include <mutex>

@@ -25,6 +25,7 @@
 //     MFMA group, after which the other U stage is known to have landed and the stage just read is refilled -- every DMA piece has a
 //     full step to land; fragments, raw windows and transform values are all produced one MFMA group ahead of their use.
 #include "csm_conv.h"
+#include "csm_convtile.h"
 #include <utility>
 #include <cstdlib>
 
@@ -88,11 +89,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void k_conv_wino(ConvArgs a, int t
 
     i32x4 ra, rb;
     {
-        uint64_t pa = (uint64_t)a.in.p, pb = (uint64_t)a.w;
-        unsigned na = (unsigned)((((int64_t)a.in.n * a.in.h * a.in.w - 1) * a.in.ld + a.in.c) * 4);
-        unsigned nb = (unsigned)((int64_t)(a.cout_g / 64) * nsteps * kUB);
-        ra = i32x4{(int)(unsigned)pa, (int)(unsigned)(pa >> 32), (int)na, 0x00020000};
-        rb = i32x4{(int)(unsigned)pb, (int)(unsigned)(pb >> 32), (int)nb, 0x00020000};
+        const uint64_t pa = (uint64_t)a.in.p, pb = (uint64_t)a.w;
+        const unsigned na = view_bytes(a.in), nb = (unsigned)((int64_t)(a.cout_g / 64) * nsteps * kUB);
+        ra = buffer_rsrc(pa, na);
+        rb = buffer_rsrc(pb, nb);
     }
     // ---- patch loader: wave w owns pieces w, w + NW, ... (a piece past the end repeats the last one: same bytes, same place) ----
     // entry e = (parity * PH + py) * PWH + pxh holds patch pixel (py, 2 pxh + parity); its 16-B slot s sits at physical slot s ^ key,
@@ -369,11 +369,10 @@ __global__ __launch_bounds__(512, 2) void k_conv_wino8(ConvArgs a, int tiles_x, 
 
     i32x4 ra, rb;
     {
-        uint64_t pa = (uint64_t)a.in.p, pb = (uint64_t)a.w;
-        unsigned na = (unsigned)((((int64_t)a.in.n * a.in.h * a.in.w - 1) * a.in.ld + a.in.c) * 4);
-        unsigned nb = (unsigned)((int64_t)(a.cout_g / 64) * nsteps * kUB);
-        ra = i32x4{(int)(unsigned)pa, (int)(unsigned)(pa >> 32), (int)na, 0x00020000};
-        rb = i32x4{(int)(unsigned)pb, (int)(unsigned)(pb >> 32), (int)nb, 0x00020000};
+        const uint64_t pa = (uint64_t)a.in.p, pb = (uint64_t)a.w;
+        const unsigned na = view_bytes(a.in), nb = (unsigned)((int64_t)(a.cout_g / 64) * nsteps * kUB);
+        ra = buffer_rsrc(pa, na);
+        rb = buffer_rsrc(pb, nb);
     }
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float *)lds;
     const unsigned voffU = (unsigned)lane * 16u;
@@ -649,7 +648,7 @@ static int launch_conv_wino_chunk(const ConvArgs &a0, hipStream_t st) {
     const int tiles_x = geo ? tx1 : tx0, tiles_y = geo ? ty1 : ty0;
     a.m_tiles = tiles_x * tiles_y * a.out.n;
     dim3 grid(a.m_tiles, a.cout_g / 64, 1);
-#ifdef CSM_WINO_DEV        // development build: CSM_WINO_VARIANT selects an ablation / option instantiation (tools/gpu/r05b.sh)
+#ifdef CSM_WINO_DEV        // development build: CSM_WINO_VARIANT selects an ablation / option instantiation (tools/wino_debug.py variants)
     const char *ve = getenv("CSM_WINO_VARIANT");
     int variant = ve ? atoi(ve) : 0;
     auto go = [&](auto kern) {

@@ -140,16 +140,24 @@ def test_f4_row_split_forms(form):
 DIRECT_LAYERS = [
     # n, h, w, cin, cout, k
     (1, 7, 9, 64, 96, 1),          # M = 63: a tail in every M tile; 96 channels: a tail in every 64- and 128-wide N tile
-    (2, 5, 6, 32, 32, 3),
+    (2, 5, 6, 32, 32, 3),          # 9 chunks: ksplit 4 cuts them into runs of 2, 2, 2 and 3
+    # two channel blocks (the patch kernels switch patch stages inside a tile; 18 chunks: the run boundary of ksplit 2 falls on the block
+    # boundary, those of ksplit 4 at chunks 4, 9 and 13 -- inside a block and on the boundary); 17 wide: a ragged 16- and 8-pixel tile
+    # column; 96 channels: a tail in every 64- and 128-wide N tile
+    (1, 9, 17, 64, 96, 3),
 ]
+DIRECT_IDS = ["1x1_64to96", "3x3_32to32", "3x3_64to96"]
+# (with ksplit 1 and 2 the serial fold only ever takes its first-run branch; the 1x1 layer has two chunks, so no ksplit 4 there)
+DIRECT_CASES = [(layer, ks) for layer in DIRECT_LAYERS for ks in (1, 2, 4) if ks <= layer[5] * layer[5] * (layer[3] // 32)]
+DIRECT_CASE_IDS = ["%s-%d" % (DIRECT_IDS[DIRECT_LAYERS.index(layer)], ks) for layer, ks in DIRECT_CASES]
 
 
-@pytest.mark.parametrize("ksplit", [1, 2])
-@pytest.mark.parametrize("layer", DIRECT_LAYERS, ids=["1x1_64to96", "3x3_32to32"])
+@pytest.mark.parametrize("layer,ksplit", DIRECT_CASES, ids=DIRECT_CASE_IDS)
 @pytest.mark.parametrize("res_mode,act", MODE_ACT, ids=IDS)
 def test_direct_kernels_every_epilogue_path(res_mode, act, layer, ksplit):
     """every configuration of the tile table (families MFMA, DMA, PATCH, DMA_P, PATCH_P, WS, NARROW; one that cannot run the layer falls
-    back) with K in one run (plain epilogue) and cut in two (ksplit 2: blocks + k_splitk_reduce, and the serial walk of one block)"""
+    back) with K in one run (plain epilogue), cut in two and cut in four (blocks + k_splitk_reduce, and the serial walk of one block:
+    only with more than two runs does its fold add to a running total)"""
     from cartoonsegmentation_amd import _lib
     from cartoonsegmentation_amd.runtime import conv_cfg_table
     n, h, w, cin, cout, k = layer
