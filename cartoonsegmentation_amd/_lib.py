@@ -61,6 +61,7 @@ def load():
         _lib.csm_webp_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_webp_scratch_bytes_m.restype = ctypes.c_size_t
         _lib.csm_png_decode_scratch_bytes.restype = ctypes.c_size_t
+        _lib.csm_gif_decode_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_jpeg_decode_progressive_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_frame_glue_scratch_bytes.restype = ctypes.c_size_t
         _lib.csm_leres_post_scratch_bytes.restype = ctypes.c_size_t

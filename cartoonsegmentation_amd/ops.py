@@ -975,6 +975,99 @@ def png_decode(files, device=None, stats=None, _infos=None):
     return out[0] if single else out
 
 
+# ---- GIF files to device frames (csrc/gifdec.hip + gifread.py; video.read_gif) ---------------------------------------------------
+# The LZW stage takes 5 B of scratch per pixel of the images of one native call (4 B source position + 1 B literal, DESIGN.md
+# §4.17), and every image is walked by one wave: 512 MiB hold about a hundred 1024 x 1024 frames, enough waves to spread over the CUs.
+GIF_DECODE_SCRATCH_BYTES = 512 << 20   # images are decoded in groups whose scratch stays below this (one image is always taken)
+_GIF_GROUP_IMAGES = 65535              # images of one native call at the most
+
+
+def gif_decode(files, device=None, alpha=False, stats=None, _infos=None):
+    """GIF files (GIF87a / GIF89a; contract DESIGN.md §4.17) to device uint8 tensors, one [n,H,W,3] in B, G, R order per file (n its
+    frames, H x W its logical screen), equal on every byte to what Pillow shows after seek(i) and convert('RGB'); with alpha=True
+    [n,H,W,4] in B, G, R, A order, equal to convert('RGBA').  `files` is one `bytes` (one tensor is returned) or a list of `bytes`
+    (a list is returned); sizes and frame counts may differ within a call.  The host walks the container (gifread.probe; a file the
+    decoder does not take raises gifread.Unsupported), joins every image's data sub-blocks and uploads only those compressed bytes
+    and the colour tables; LZW decoding, interlace, transparency, the colour tables and the disposal methods run on the device
+    (csm_gif_decode).  The LZW stage works on groups of consecutive images whose scratch stays below GIF_DECODE_SCRATCH_BYTES, one
+    native call per group, so a clip larger than the budget still decodes; only the images' indices (1 byte per pixel) stay until
+    the last call composes the frames, and the result does not depend on the budget.  Corrupt LZW data raises CsmError.  The
+    tensors of a call are views of one allocation.  `stats` (a dict) receives 'groups' (the images of every native call) and
+    'rounds' (per native call the pointer-doubling rounds launched and the rounds that did work)."""
+    import ctypes
+    from . import gifread
+    single, datas = _byte_files(files, "gif_decode")
+    infos = _infos if _infos is not None else [gifread.probe(d) for d in datas]
+    dev = _gpu_device(device, "gif_decode")
+    L = _lib.load()
+    words = L.csm_gif_decode_desc_words()
+    assert words == gifread.DESC_WORDS == gifread.FILE_WORDS
+    channels = 4 if alpha else 3
+    a16 = lambda v: (v + 15) & ~15
+    # the blob: per file its global table, per image with one its local table (768 bytes each, zero-padded), then every image's
+    # LZW bytes, each on a 16-byte boundary and padded to one
+    rows, frows, tables, streams, own = [], [], [], [], []
+    o, idx_off, out_off = 0, 0, 0
+    shapes = []
+    for j, (d, info) in enumerate(zip(datas, infos)):
+        frows.append(gifread.file_descriptor(info, len(rows), out_off, channels))
+        n, H, W = len(info['frames']), info['height'], info['width']
+        shapes.append((out_off, n, H, W))
+        out_off += a16(n * H * W * channels)
+        gpal = None
+        if info['global_palette'] is not None:
+            gpal = o
+            tables.append((o, info['global_palette']))
+            o += 768
+        for fr in info['frames']:
+            pal_off = gpal
+            if fr['palette'] is not None:
+                pal_off = o
+                tables.append((o, fr['palette']))
+                o += 768
+            rows.append([fr, j, d, pal_off, len(gifread.palette_of(info, fr)) // 3, idx_off])
+            npix = fr['height'] * fr['width']
+            idx_off += a16(npix)
+            own.append(a16(npix) + a16(4 * npix))
+    for r in rows:
+        r.append(o)
+        o += a16(r[0]['stream_bytes'])
+    blob_h = _np.zeros(max(o, 16), _np.uint8)
+    for at, t in tables:
+        blob_h[at:at + len(t)] = _np.frombuffer(t, _np.uint8)
+    desc = _np.zeros((len(rows), words), _np.int32)
+    for i, (fr, j, d, pal_off, entries, ioff, soff) in enumerate(rows):
+        blob_h[soff:soff + fr['stream_bytes']] = gifread.lzw_stream(d, fr)
+        desc[i] = gifread.image_descriptor(fr, j, soff, pal_off, entries, ioff)
+    fdesc = _np.stack(frows)
+    c_desc = ctypes.POINTER(ctypes.c_int32)
+    table_args = [desc.ctypes.data_as(c_desc), i32(desc.shape[0]), fdesc.ctypes.data_as(c_desc), i32(fdesc.shape[0])]
+    groups = []
+    for i, k in _budget_chunks(own, GIF_DECODE_SCRATCH_BYTES):
+        groups += [(s, min(_GIF_GROUP_IMAGES, i + k - s)) for s in range(i, i + k, _GIF_GROUP_IMAGES)]
+    rounds = []
+    with torch.cuda.device(dev):
+        blob = torch.from_numpy(blob_h).to(dev)
+        idx = torch.empty(idx_off, dtype=torch.uint8, device=dev)
+        pixels = torch.empty(out_off, dtype=torch.uint8, device=dev)
+        for gi, (first, count) in enumerate(groups):
+            need = L.csm_gif_decode_scratch_bytes(*table_args, i32(first), i32(count))
+            if need == 0:
+                raise _lib.CsmError("gif_decode: %s" % L.csm_last_error().decode())
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+            last = gi == len(groups) - 1
+            info_h = (ctypes.c_int * 4)()
+            check(L.csm_gif_decode(ptr(blob), i64(blob.numel()), *table_args, i32(first), i32(count), ptr(idx), i64(idx_off),
+                                   ptr(pixels) if last else ctypes.c_void_p(0), i64(out_off if last else 0), i32(channels), ptr(scratch),
+                                   info_h, stream_ptr(dev)), "gif_decode")
+            rounds.append((int(info_h[0]), int(info_h[1])))
+    if stats is not None:
+        stats['groups'] = [k for _, k in groups]
+        stats['rounds'] = rounds
+    out = [pixels[o:o + n * H * W * channels].view(n, H, W, channels) for o, n, H, W in shapes]
+    return out[0] if single else out
+
+
 # ---- WebP files to device frames (csrc/webpdec.hip, csrc/webplossy.hip + webpread.py; utils.io_utils.imread_device) ------------
 WEBP_DECODE_SCRATCH_BYTES = 64 << 20   # files are decoded in chunks whose scratch stays below this (one file is always taken)
 WEBP_LOSSY_DECODE_SCRATCH_BYTES = 64 << 20   # the same for the lossy files of a call, which go to native calls of their own

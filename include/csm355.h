@@ -656,6 +656,38 @@ int csm_png_decode_desc_words(void);
 int csm_png_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, uint8_t *out, int64_t out_bytes,
                    void *scratch, int *info_host, void *stream);
 
+/* GIF files (GIF87a / GIF89a, animated or not) to uint8 B, G, R or B, G, R, A frames (gifdec.hip; contract DESIGN.md §4.17, restated
+ * in tests/gifdec_restatement.py: frame i equals what Pillow shows after seek(i) on every byte).  The host parses the container
+ * (cartoonsegmentation_amd/gifread.py) and hands over one blob of device bytes (every image's joined LZW sub-blocks and the colour
+ * tables), one descriptor per image and one per file; files of different sizes and frame counts share a call.  A call does two
+ * things, either of which may be empty: it decodes the LZW data of the images [first, first + count) into idx (1 byte per pixel,
+ * stream order), and, when out is not NULL, composes every frame of every file from idx.  So a clip whose images do not fit the
+ * scratch one wants to spend is decoded by several calls over groups of images, the last of which (or one more with count = 0)
+ * passes out; idx is what stays between them.
+ * desc_host: host int32 [n][csm_gif_decode_desc_words() = 16], the images of file 0, then of file 1, ...: [0] [1] height and width of
+ *   the image's rectangle, [2] [3] its top and left on the logical screen, [4] [5] offset (a multiple of 16) and length of its LZW
+ *   bytes in the blob, whose bytes reach to the stream's end rounded up to 16, [6] minimum code size (2 .. 8), [7] bit 0: interlaced,
+ *   [8] transparent index or -1, [9] disposal (0 keep, 2 to background, 3 to previous), [10] offset (a multiple of 16) of the frame's
+ *   colour table in the blob, 768 bytes R, G, B, zero-padded, [11] its entries (1 .. 256), [12] [13] the byte offset of the image's
+ *   indices in idx (low 31 bits, the bits above; a multiple of 16; an image takes its pixels rounded up to 16), [14] its file, [15] 0.
+ * file_desc_host: host int32 [n_files][16]: [0] [1] height and width of the logical screen, [2] [3] first image and image count,
+ *   [4] [5] the byte offset of the file's frames in out (low 31 bits, the bits above; a multiple of 4), [6] background index,
+ *   [7] bit 0: frame 0 declares a transparent index (the canvas carries alpha), the rest 0.
+ * out: u8, file j at its offset as [frames][H][W][channels], channels 3 (B, G, R) or 4 (B, G, R, A).  blob, idx, out and scratch are
+ *   16-byte aligned.
+ * scratch: csm_gif_decode_scratch_bytes(...) device bytes (0 for invalid descriptors): per pixel of the group's images 4 B of source
+ *   positions and 1 B of literals, plus 132 B per image of the group, 88 B per image and 32 B per file of the call.
+ * csm_gif_decode: info_host (may be NULL) receives [0] the pointer-doubling rounds launched, [1] the rounds that did work.  With
+ *   count > 0 the call SYNCHRONISES the stream once, at the end (one error word per image, bits as in csrc/csm_lzw.h), and returns
+ *   CSM_ERR_DATA for corrupt LZW data (a code above the next free entry, a first code that is no literal, data or the end code
+ *   before the rectangle is full; data behind a full rectangle are ignored); whatever the data, no read or store leaves the image's
+ *   own ranges.  No kernel waits on another workgroup; the output is deterministic. */
+size_t csm_gif_decode_scratch_bytes(const int32_t *desc_host, int n, const int32_t *file_desc_host, int n_files, int first, int count);
+int csm_gif_decode_desc_words(void);
+int csm_gif_decode(const uint8_t *blob, int64_t blob_bytes, const int32_t *desc_host, int n, const int32_t *file_desc_host, int n_files,
+                   int first, int count, uint8_t *idx, int64_t idx_bytes, uint8_t *out, int64_t out_bytes, int channels,
+                   void *scratch, int *info_host, void *stream);
+
 /* Lossless WebP files (VP8L) to uint8 B, G, R or B, G, R, A pixels (webpdec.hip; contract DESIGN.md §4.15, restated in
  * tests/webpdec_restatement.py: the result equals what libwebp decodes on every byte).  The host parses the RIFF container
  * (cartoonsegmentation_amd/webpread.py) and hands over one blob of device bytes and one descriptor per file; files of different

@@ -30,7 +30,7 @@ def imread(path):
         return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
 
 
-def imread_device_many(paths, device=None, stats=None, progressive=None, webp=None, webp_lossy=None):
+def imread_device_many(paths, device=None, stats=None, progressive=None, webp=None, webp_lossy=None, gif=None):
     """imread for a list of paths with the pixels on the device: a list of uint8 BGR [H,W,3] tensors.  A .jpg / .jpeg file that the
     device decoder takes (cartoonsegmentation_amd.jpegcode.probe: baseline, Huffman, grey or Y Cb Cr at 4:4:4 / 4:2:2 / 4:2:0) and
     whose EXIF orientation is 1 or absent is decoded on the MI355X by ops.jpeg_decode, all such files in one call: only the file's
@@ -56,9 +56,16 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
     only together with the webp option: the lossy .webp files that webpread.probe(data, lossy=True) accepts (a VP8 key frame with or
     without an ALPH chunk, not animated, orientation 1 or absent) then go to the device as well (equal to imread on
     every byte), in the same ops.webp_decode call as the lossless ones.  `stats['webp']` lists them with the lossless files, and
-    `stats` also receives 'webp_lossy', the indices of the lossy ones.  With the option off, routing and `stats` are unchanged."""
+    `stats` also receives 'webp_lossy', the indices of the lossy ones.  With the option off, routing and `stats` are unchanged.
+
+    gif=True (None reads the environment variable CSM_DEVICE_DECODE_GIF, '1' = on; the default is off) also sends every .gif file
+    that cartoonsegmentation_amd.gifread.probe accepts to the device (ops.gif_decode, DESIGN.md §4.17: equal on every byte to what
+    PIL shows, which for the first frame is what imread returns), all such files in one call, and returns frame 0 of each.  `stats`
+    then also receives 'gif', the indices of those files.  With the option off, routing and `stats` are unchanged."""
     import torch
-    from cartoonsegmentation_amd import jpegcode, ops, pngread, webpread
+    from cartoonsegmentation_amd import gifread, jpegcode, ops, pngread, webpread
+    if gif is None:
+        gif = os.environ.get('CSM_DEVICE_DECODE_GIF', '0') == '1'
     if webp is None:
         webp = os.environ.get('CSM_DEVICE_DECODE_WEBP', '0') == '1'
     if webp_lossy is None:
@@ -71,6 +78,7 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
     idx, datas, infos = [], [], []
     pidx, pdatas, pinfos = [], [], []
     widx, wdatas, winfos = [], [], []
+    gidx, gdatas, ginfos = [], [], []
     host = []
     for i, path in enumerate(paths):
         suffix = Path(str(path)).suffix.lower()
@@ -104,6 +112,16 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
             if info is not None:
                 widx.append(i); wdatas.append(data); winfos.append(info)
                 continue
+        elif suffix == '.gif' and gif:
+            with open(path, 'rb') as f:
+                data = f.read()
+            try:
+                info = gifread.probe(data)
+            except gifread.Unsupported:
+                info = None
+            if info is not None:
+                gidx.append(i); gdatas.append(data); ginfos.append(info)
+                continue
         host.append(i)
         out[i] = torch.from_numpy(imread(path)).to(dev)
     if datas:
@@ -112,6 +130,9 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
     if pdatas:
         for i, t in zip(pidx, ops.png_decode(pdatas, dev, _infos=pinfos)):
             out[i] = t
+    if gdatas:
+        for i, t in zip(gidx, ops.gif_decode(gdatas, dev, _infos=ginfos)):
+            out[i] = t[0]
     while wdatas:
         try:
             for i, t in zip(widx, ops.webp_decode(wdatas, dev, _infos=winfos, lossy=webp_lossy)):
@@ -129,6 +150,8 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
         stats.update(jpeg=idx, png=pidx, host=host)
         if webp:
             stats['webp'] = widx
+        if gif:
+            stats['gif'] = gidx
         if webp_lossy:
             stats['webp_lossy'] = [i for i, info in zip(widx, winfos) if info['kind'] == 'lossy']
         if progressive:
@@ -136,9 +159,9 @@ def imread_device_many(paths, device=None, stats=None, progressive=None, webp=No
     return out
 
 
-def imread_device(path, device=None, progressive=None, webp=None, webp_lossy=None):
+def imread_device(path, device=None, progressive=None, webp=None, webp_lossy=None, gif=None):
     """imread with the pixels on the device: see imread_device_many"""
-    return imread_device_many([path], device, progressive=progressive, webp=webp, webp_lossy=webp_lossy)[0]
+    return imread_device_many([path], device, progressive=progressive, webp=webp, webp_lossy=webp_lossy, gif=gif)[0]
 
 
 def imwrite(img, file_path, auto_mkdir=True):
