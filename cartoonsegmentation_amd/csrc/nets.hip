@@ -214,8 +214,49 @@ static int run_ops(const csm_op *ops, int n_ops, const csm_tensor_desc *tensors,
                 if (rc) return rc;
                 break;
             }
+            case CSM_OP_ATTENTION_RELPOS: {
+                const int heads = op.groups, d = op.cin_g;
+                if (heads < 1 || in.c != 3 * heads * d || out.c != heads * d || out.n != in.n || out.h * out.w != in.h * in.w || op.aux_off < 0) { csm::set_error("op %d: attention_relpos operands", i); return CSM_ERR_ARG; }
+                rc = csm::launch_attention_relpos(in.p, in.ld, out.p, out.ld, in.n, in.h * in.w, heads, d, weights + op.aux_off, op.kh, op.kw, st);
+                if (rc) return rc;
+                break;
+            }
+            case CSM_OP_CROSS_ATTENTION: {
+                const int heads = op.groups, d = op.cin_g;
+                if (heads < 1 || op.in1 < 0 || in.c != heads * d || in1.c != 2 * heads * d || out.c != heads * d || in1.n != in.n || out.n != in.n || out.h * out.w != in.h * in.w) { csm::set_error("op %d: cross_attention operands", i); return CSM_ERR_ARG; }
+                rc = csm::launch_cross_attention(in.p, in.ld, in1.p, in1.ld, out.p, out.ld, in.n, in.h * in.w, in1.h * in1.w, heads, d, st);
+                if (rc) return rc;
+                break;
+            }
+            case CSM_OP_CHANNEL_DOT: {
+                if (op.in1 < 0 || in1.c != in.c || in1.n != in.n || in1.h * in1.w != 1 || out.n != in.n || out.h != in.h || out.w != in.w) { csm::set_error("op %d: channel_dot operands", i); return CSM_ERR_ARG; }
+                rc = csm::launch_channel_dot(in.p, in.ld, in1.p, in1.ld, out.p, out.ld, in.n, (int64_t)in.h * in.w, in.c, st);
+                if (rc) return rc;
+                break;
+            }
             case CSM_OP_TOKENS: {
                 const int mode = op.flags;
+                if (mode == 3 || mode == 4) {          // window partition / un-partition (sam.hip); kh = window size
+                    const View &map = mode == 3 ? in : out, &win = mode == 3 ? out : in;
+                    const int ws = op.kh, wy = ws > 0 ? (map.h + ws - 1) / ws : 0, wx = ws > 0 ? (map.w + ws - 1) / ws : 0;
+                    if (ws < 1 || in.c != out.c || win.n != map.n * wy * wx || win.h * win.w != ws * ws ||
+                        (mode == 4 && op.in1 >= 0 && (in1.n != out.n || in1.h != out.h || in1.w != out.w || in1.c != out.c)) || (mode == 3 && op.in1 >= 0)) {
+                        csm::set_error("op %d: tokens operands (mode %d)", i, mode); return CSM_ERR_ARG;
+                    }
+                    rc = csm::launch_window(mode == 4, in.p, in.ld, op.in1 >= 0 ? in1.p : nullptr, op.in1 >= 0 ? in1.ld : 0, out.p, out.ld, map.n, map.h, map.w, ws, in.c, st);
+                    if (rc) return rc;
+                    break;
+                }
+                if (mode == 5 || mode == 6) {          // broadcast add (sam.hip)
+                    const int64_t np = (int64_t)out.h * out.w;
+                    if (in.c != out.c || (int64_t)in.h * in.w != np || (op.in1 >= 0 && (in1.c != out.c || (int64_t)in1.h * in1.w != np)) || (mode == 6 && op.aux_off < 0)) {
+                        csm::set_error("op %d: tokens operands (mode %d)", i, mode); return CSM_ERR_ARG;
+                    }
+                    rc = csm::launch_bcast_add(in.p, in.ld, in.n, op.in1 >= 0 ? in1.p : nullptr, op.in1 >= 0 ? in1.ld : 0, op.in1 >= 0 ? in1.n : 1, out.p, out.ld, out.n, np,
+                                               out.c, op.aux_off >= 0 ? weights + op.aux_off : nullptr, mode == 6, st);
+                    if (rc) return rc;
+                    break;
+                }
                 const int np = mode == 0 ? in.h * in.w : out.h * out.w;
                 const bool ok = mode == 0 ? (out.h == np + 1 && out.w == 1 && out.c == in.c && op.aux_off >= 0)
                                           : (in.h == np + 1 && in.w == 1 && out.c == (mode == 1 ? 2 : 1) * in.c);

@@ -28,6 +28,7 @@ from ._lib import check, f32, i32, i64, ptr, stream_ptr
 from .anime_instances import AnimeInstances
 from .nets import build_disparity, build_inpaint_context, build_inpaint_grid, build_leres, build_refine, build_semantics
 from .runtime import CompiledProgram
+from .sam import Sam
 from .segmentation import AnimeInsSeg, scaledown_size
 from .weights import StateDictWeights, SynthWeights
 
@@ -75,6 +76,7 @@ class KenBurnsConfig:
     sd_img2img_url: str = 'http://127.0.0.1:7860/sdapi/v1/img2img'
     ldm_inpaint_options: dict = field(default_factory=dict)
     ldm_inpaint_size: int = 0
+    sam_ckpt: str = 'models/sam/sam_vit_h_4b8939.pth'      # detector 'sam' (env CSM_SAM_CKPT overrides; not a field of the reference's dataclass)
     instances: AnimeInstances = None
     # run-time state (not constructor fields in the reference either)
     disparity_min = 0
@@ -194,6 +196,7 @@ class KenBurnsPipeline:
             raise _lib.CsmError("KenBurnsPipeline needs an MI355X: libcsm355 has no CPU path")
         self.device = torch.device('cuda:%d' % torch.cuda.current_device()) if device in (None, 'cuda') else torch.device(device)
         self.animeinsseg = None
+        self.sam = None
         self._leres, self._leres_weights, self._leres_ws = {}, {}, None
         self._refine_ws, self._refine_progs = None, {}
         self.max_instances = 100                 # AnimeInsSeg.infer default (animeinsseg/__init__.py:417)
@@ -212,8 +215,8 @@ class KenBurnsPipeline:
 
     # ---- component selection (kenburns_effect.py:425-440, :514-546) ---------------------------------
     def set_detector(self, detector: str):
-        if detector != 'animeinsseg':
-            raise NotImplementedError("detector %r: only 'animeinsseg' is on the hot path" % detector)
+        if detector not in ('animeinsseg', 'sam'):
+            raise NotImplementedError("detector %r: 'animeinsseg' and 'sam' are on the hot path" % detector)
         if self.animeinsseg is None:
             ckpt = self.cfg.det_ckpt
             if not os.path.exists(ckpt):
@@ -223,6 +226,21 @@ class KenBurnsPipeline:
             # kenburns_effect.py:832-837: AnimeInsSeg(cfg.det_ckpt, device) -- the reference never applies cfg.det_size
             # (SURVEY F8); callers that want another detector size use animeinsseg.set_detect_size / infer(det_size=)
             self.animeinsseg = AnimeInsSeg(ckpt, device=str(self.device))
+        if detector == 'sam' and self.sam is None:           # kenburns_effect.py:838-841: the same detector, its masks replaced by SAM's
+            self.sam = Sam(self.cfg.sam_ckpt, device=self.device)
+        self.detector = detector
+
+    def forward_sam(self, img):
+        """kenburns_effect.py:848-860: RTMDet-Ins instances without mask refinement, their boxes as integer xyxy prompts, their masks
+        replaced by SAM's.  The boxes are read from the device tensor and the masks stay on the device (the reference goes through
+        Python lists and numpy)"""
+        inst = self.animeinsseg.infer(img, self.cfg.pred_score_thr, None, output_type='tensor', max_instances=self.max_instances)
+        if inst.is_empty:
+            return inst
+        xyxy = inst.bboxes.to(device=self.device, dtype=torch.int32).clone()
+        xyxy[:, 2:] += xyxy[:, :2]
+        inst.masks, _ = self.sam.set_image(self.animeinsseg._upload(img)).predict_boxes(xyxy)
+        return inst
 
     def set_depth_estimation(self, depth_est: str):
         if depth_est == 'default':                       # kenburns_effect.py:547-548: the original 3D-Ken-Burns estimator
@@ -525,6 +543,8 @@ class KenBurnsPipeline:
         if scale_down_to_maxsize:                                                                                    # :862-863
             from utils.io_utils import scaledown_maxsize
             img = scaledown_maxsize(img, self.cfg.max_size)
+        if self.detector == 'sam':
+            return self.forward_sam(img), img
         inst = self.animeinsseg.infer(img, self.cfg.pred_score_thr, self.cfg.mask_refine_kwargs or None, output_type='tensor',
                                       max_instances=self.max_instances)                                              # :869-872
         return inst, img
@@ -593,6 +613,8 @@ class KenBurnsPipeline:
             frames_d = [self._scaled_frame(t) for t in imgs_d]
             seg = lambda: self.animeinsseg.infer(list(imgs_d), self.cfg.pred_score_thr, self.cfg.mask_refine_kwargs or None,
                                                  output_type='tensor', max_instances=self.max_instances)
+            if self.detector == 'sam':
+                seg = lambda: [self.forward_sam(t) for t in imgs_d]             # noqa: E731
             # the batched estimator exists for LeReS only; any other selected estimator runs frame by frame (same results as
             # generate_kenburns_config), still on the side stream when overlap is on
             batched_leres = self._depth_est == self._depth_est_leres

@@ -15,6 +15,7 @@ import numpy as np
 OP_CONV, OP_DWCONV, OP_MAXPOOL, OP_BILINEAR, OP_NEAREST, OP_ADD, OP_GAVGPOOL, OP_SCALE = 1, 2, 3, 4, 5, 6, 7, 8
 OP_NCHW_TO_NHWC, OP_NHWC_TO_NCHW, OP_ACT, OP_COPY, OP_ATTRACTOR, OP_LOGBINOM = 9, 10, 11, 12, 13, 14
 OP_LAYERNORM, OP_ATTENTION, OP_TOKENS, OP_DEPTH_TO_SPACE = 15, 16, 17, 18
+OP_ATTENTION_RELPOS, OP_CROSS_ATTENTION, OP_CHANNEL_DOT = 19, 20, 21
 ACT = {None: 0, 'none': 0, 'relu': 1, 'silu': 2, 'prelu': 3, 'hsigmoid': 4, 'sigmoid': 5, 'softplus': 6, 'gelu': 7}
 
 
@@ -532,6 +533,72 @@ class Program:
         w1 = w.transpose(2, 3, 1, 0).reshape(k * k * cout, cin, 1, 1)
         b1 = None if b is None else np.tile(np.asarray(b, np.float32), k * k)
         return self.depth_to_space(self.conv(x, w1, b1), k)
+
+    # ---- Segment Anything ops (csrc/sam.hip; include/csm355.h) ------------------------------------------------------------------------
+    def attention_relpos(self, qkv, heads, grid, rel_h, rel_w):
+        """softmax(q k^T + q.Rh[yi - yj + gh - 1] + q.Rw[xi - xj + gw - 1]) v per head on a gh x gw token grid (N = qkv.h * qkv.w tokens, row
+        major); qkv [n, ., ., 3 * heads * d] with q pre-scaled by d^-0.5; rel_h [2 gh - 1, d], rel_w [2 gw - 1, d] as the checkpoint has them
+        (products with the UNSCALED q): packed as (Rh ; Rw) * sqrt(d)"""
+        d = qkv.c // (3 * heads)
+        gh, gw = grid
+        assert qkv.c == 3 * heads * d and d in (32, 64, 80, 128) and qkv.h * qkv.w == gh * gw, (qkv.shape, heads, grid)
+        rel_h, rel_w = np.asarray(rel_h, np.float32), np.asarray(rel_w, np.float32)
+        assert rel_h.shape == (2 * gh - 1, d) and rel_w.shape == (2 * gw - 1, d), (rel_h.shape, rel_w.shape, grid, d)
+        out = self.buffer(qkv.n, qkv.h, qkv.w, heads * d)
+        tab = np.concatenate([rel_h, rel_w]) * np.sqrt(np.float32(d))
+        a_h, a_n = self._w(tab, tab)
+        fl = qkv.n * heads * (4 * gh * gw * gh * gw * d + 2 * gh * gw * (2 * gh + 2 * gw - 2) * d)
+        self.flops += fl
+        self.flops_exec += fl
+        return self._emit(OP_ATTENTION_RELPOS, qkv, None, out, groups=heads, cin_g=d, kh=gh, kw=gw, aux_off=a_h, nat=dict(aux_off=a_n))
+
+    def cross_attention(self, q, kv, heads):
+        """softmax(q k^T) v per head between two token sets: q [n, Nq tokens, heads * d] (pre-scaled), kv [n, Nk tokens, 2 * heads * d]
+        (k | v) -> [n, Nq tokens, heads * d]"""
+        d = q.c // heads
+        assert q.c == heads * d and kv.c == 2 * q.c and kv.n == q.n and d in (2, 4, 8, 16, 32, 64), (q.shape, kv.shape, heads)
+        out = self.buffer(q.n, q.h, q.w, q.c)
+        self.flops += 4 * q.n * q.h * q.w * kv.h * kv.w * q.c
+        self.flops_exec += 4 * q.n * q.h * q.w * kv.h * kv.w * q.c
+        return self._emit(OP_CROSS_ATTENTION, q, kv, out, groups=heads, cin_g=d)
+
+    def channel_dot(self, x, h):
+        """out[n, y, x] = sum_c x[n, y, x, c] * h[n, 0, 0, c] -> [n, h, w, 1] (stored in a 4-channel buffer)"""
+        assert h.n == x.n and h.h * h.w == 1 and h.c == x.c and x.c % 4 == 0, (x.shape, h.shape)
+        out = self.buffer(x.n, x.h, x.w, 4).slice(0, 1)
+        return self._emit(OP_CHANNEL_DOT, x, h, out)
+
+    def window_partition(self, x, ws):
+        """[n, gh, gw, c] -> [n * ceil(gh / ws) * ceil(gw / ws), ws * ws, 1, c], zero padded"""
+        wy, wx = -(-x.h // ws), -(-x.w // ws)
+        out = self.buffer(x.n * wy * wx, ws * ws, 1, x.c)
+        return self._emit(OP_TOKENS, x, None, out, flags=3, kh=ws)
+
+    def window_unpartition(self, xw, ws, like, res=None):
+        """the inverse onto the map shape of `like` [n, gh, gw, c] (padding dropped), plus the residual `res`"""
+        out = self.buffer(like.n, like.h, like.w, xw.c)
+        return self._emit(OP_TOKENS, xw, res, out, flags=4, kh=ws)
+
+    def broadcast_add(self, a, b=None, const=None, per_position=False, n=None):
+        """out[i] = a[i % a.n] (+ b[i % b.n]) (+ const): const is one vector per channel, or (per_position) one per position and channel"""
+        n = n or max(a.n, b.n if b is not None else 1)
+        out = self.buffer(n, a.h, a.w, a.c)
+        a_h = a_n = -1
+        if const is not None:
+            const = np.asarray(const, np.float32).reshape(-1)
+            assert const.size == (a.h * a.w * a.c if per_position else a.c), (const.size, a.shape)
+            a_h, a_n = self._w(const, const)
+        return self._emit(OP_TOKENS, a, b, out, flags=6 if per_position else 5, aux_off=a_h, nat=dict(aux_off=a_n))
+
+    def reshape(self, x, n, h, w, c):
+        """the same storage under another NHWC shape, as a VIEW (a token sequence [n, T, 1, c] as [n, 1, 1, T c]: channel slices of it are
+        single tokens)"""
+        assert x.coff == 0 and x.c == x.buf.c and x.buf.ext < 0 and n * h * w * c == x.n * x.h * x.w * x.c, (x.shape, (n, h, w, c))
+        b = Buf(n, h, w, c)
+        b.alias = x.buf
+        b.first, b.last = x.buf.first, x.buf.last
+        self.bufs.append(b)
+        return T(self, b, 0, c)
 
     def crop_rows(self, x, h):
         """the first h rows of a single-image map as a VIEW (torch's negative bottom pad): same buffer, smaller height"""

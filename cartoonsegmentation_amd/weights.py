@@ -54,6 +54,8 @@ def synth_tensor(name, shape, kind):
         v = 0.5 * u
     elif kind == 'rel_bias':     # relative-position-bias table: logits of order one, so that the bias visibly shapes the softmax
         v = 1.5 * u
+    elif kind == 'unit':         # unit-variance draws (SAM's Gaussian positional-encoding matrix)
+        v = u * np.sqrt(3.0)
     elif kind == 'layer_scale':  # BEiT gamma_1 / gamma_2 (trained values are O(0.1 .. 1))
         v = 0.3 + 0.2 * u
     else:

@@ -225,8 +225,25 @@ enum csm_op_kind {
                                row 0 = class token (aux_off -> c floats); 1 "readout project input" in0 = tokens [n, N, 1, c] ->
                                out [n, kh, kw, 2c] = (token 1 + i | class token) (MiDaS ProjectReadout's concat); 2 "readout ignore"
                                -> out [n, kh, kw, c] = token 1 + i (MiDaS Slice) */
-    CSM_OP_DEPTH_TO_SPACE = 18 /* out[n, y*k + ky, x*k + kx, c] = in0[n, y, x, (ky*k + kx) * out.c + c], k = stride: the scatter half of a
+    CSM_OP_DEPTH_TO_SPACE = 18, /* out[n, y*k + ky, x*k + kx, c] = in0[n, y, x, (ky*k + kx) * out.c + c], k = stride: the scatter half of a
                                ConvTranspose2d(kernel = stride = k) whose GEMM half is a 1x1 CSM_OP_CONV to k*k*cout channels */
+    /* Segment Anything (segment_anything's ImageEncoderViT / PromptEncoder / MaskDecoder, boxes only; csrc/sam.hip).  Same
+     * tolerance-level status as the three transformer ops above.  CSM_OP_TOKENS gains the modes
+     *   3 "window partition": in0 [n, gh, gw, c] -> out [n * wy * wx, kh * kh, 1, c], wy = ceil(gh / kh), wx = ceil(gw / kh): window
+     *     (b, iy, ix) is sample (b * wy + iy) * wx + ix, its token ty * kh + tx the pixel (iy kh + ty, ix kh + tx), ZEROS beyond the map;
+     *   4 "window un-partition": the inverse, padding dropped: out [n, gh, gw, c] = in0 [n * wy * wx, kh * kh, 1, c] (+ in1 [n, gh, gw, c]);
+     *   5 / 6 "broadcast add": out[b, p, :] = in0[b % in0.n, p, :] (+ in1[b % in1.n, p, :]) (+ aux); in0.n and in1.n are 1 or out.n;
+     *     aux_off -> c floats (mode 5, optional) or h * w * c floats, one vector per position (mode 6). */
+    CSM_OP_ATTENTION_RELPOS = 19, /* self-attention with the decomposed relative position bias.  in0 = qkv [n, ., ., 3 * heads * d] with
+                               N = h * w = kh * kw tokens, token y * kw + x = grid position (y, x) (q | k | v head-major, q carrying
+                               1/sqrt(d)); out [n, ., ., heads * d]; groups = heads, cin_g = d in {32, 64, 80, 128}.
+                               out[i, h, :] = sum_j softmax_j(q_i . k_j + q_i . R[yi - yj + kh - 1] + q_i . R[2 kh - 1 + xi - xj + kw - 1]) v_j
+                               aux_off -> R [(2 kh - 1) + (2 kw - 1)][d]: the height table, then the width table, shared by the heads and
+                               multiplied by sqrt(d) by the host (the q of the product is the scaled one) */
+    CSM_OP_CROSS_ATTENTION = 20,  /* in0 = q [n, Nq tokens, heads * d] (scaled), in1 = [n, Nk tokens, 2 * heads * d] (k | v, head-major)
+                               -> out [n, Nq, heads * d] = softmax_j(q_i . k_j) v_j per head; groups = heads, cin_g = d in
+                               {2, 4, 8, 16, 32, 64}; any Nq, Nk (token count = h * w) */
+    CSM_OP_CHANNEL_DOT = 21       /* out[n, y, x, 0] = sum_c in0[n, y, x, c] * in1[n, 0, 0, c], ascending c, one fmaf chain from 0 */
 };
 enum csm_act { CSM_ACT_NONE = 0, CSM_ACT_RELU = 1, CSM_ACT_SILU = 2, CSM_ACT_PRELU = 3, CSM_ACT_HSIGMOID = 4,
                CSM_ACT_SIGMOID = 5, CSM_ACT_SOFTPLUS = 6 /* torch.nn.Softplus(): x > 20 ? x : log(1 + exp(x)) */,
@@ -354,6 +371,22 @@ int csm_debug_attention_options(int options);
 int csm_run_program_profile(const csm_op *ops, int n_ops, const csm_tensor_desc *tensors, int n_tensors,
                             const float *weights, float *workspace, void *const *ext, int n_ext, void *stream,
                             float *op_ms);
+
+/* ------------------------------------------------------------------------------------
+ * Segment Anything glue (segment_anything's SamPredictor / ResizeLongestSide / Sam.preprocess / Sam.postprocess_masks; csrc/sam.hip)
+ * ---------------------------------------------------------------------------------- */
+/* bgr: DEVICE uint8 [H, W, 3] -> out: DEVICE float NCHW [3, S, S] = RGB, bilinear (align_corners = False, no antialiasing) to nh x nw,
+ * (v - mean) / std with mean (123.675, 116.28, 103.53) and std (58.395, 57.12, 57.375), zeros beyond (nh, nw).  (segment_anything resizes
+ * the uint8 image through PIL instead: a deliberate, documented difference.) */
+int csm_sam_preprocess(const uint8_t *bgr, int H, int W, int S, int nh, int nw, float *out, void *stream);
+/* logits: DEVICE float [n, L, L] -> masks: DEVICE uint8 (0 / 1) [n, H, W]: bilinear to S x S, crop to [nh, nw], bilinear to H x W
+ * (both align_corners = False), > 0 -- one pass, nothing in between is stored. */
+int csm_sam_postprocess(const float *logits, int n, int L, int S, int nh, int nw, int H, int W, uint8_t *masks, void *stream);
+/* boxes: DEVICE float [n, 4] xyxy, multiplied by (sx, sy) into the model's S x S input frame -> tokens: DEVICE float NCHW
+ * [n, C, n_static + 2, 1]: the n_static constant output tokens, then the two corner embeddings sin | cos(2 pi (2 (p + 0.5) / S - 1) . gauss)
+ * + point embedding.  consts: DEVICE float [n_static][C] tokens, [2][C] point embeddings 2 and 3, [2][C / 2] the Gaussian matrix. */
+int csm_sam_box_tokens(const float *boxes, int n, double sx, double sy, int S, const float *consts, int C, int n_static, float *tokens,
+                       void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Glue around the Inpaint / Refine nets, the depth-adjustment resize branch and AnimeInstances.resize (rounds 1-2 used torch ops here)
