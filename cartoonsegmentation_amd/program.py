@@ -92,13 +92,23 @@ CONV_FLAG_GROUPED = 16
 _CHAIN8 = (0, 4, 1, 5, 2, 6, 3, 7)
 
 
-def grouped_valu_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ld=None, h=0, w=0):
+def _view16(ld, off):
+    """a view whose pixels all start on a 16-byte boundary: pitch and channel offset are multiples of 4 floats (a planned buffer starts on
+    a 64-float boundary of a workspace that is at least 256-byte aligned)"""
+    return ld % 4 == 0 and off % 4 == 0
+
+
+def grouped_valu_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ld=None, h=0, w=0, out_ld=None, out_off=0, res_ld=None, res_off=0):
     """(mirrors csrc/grouped.hip::grouped_eligible, including its 32-bit byte-offset bound on ONE sample's input view: the weights of a
-    flagged op exist in the vector kernel's image only, so a layer the kernel would refuse must not be flagged)"""
+    flagged op exist in the vector kernel's image only, so a layer the kernel would refuse must not be flagged).  out_ld / out_off and
+    res_ld / res_off: channel pitch and channel offset of the output and of the residual view (None: a buffer of its own / no residual)
+    -- the kernel stores and fetches them as float4, so both must be 16-byte aligned at every pixel; a layer that is not lowers to the
+    block-diagonal form, whose epilogue (csrc/csm_conv.h::conv_tail) stores single floats"""
     c = groups * cin_g
     return (GROUPED_VALU and groups > 1 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and dil == 1 and cout == c
             and cin_g in (8, 16, 32) and cin_g <= GROUPED_VALU_MAX_CG and c % 32 == 0 and (ld is None or ld % 4 == 0)
-            and h * w * (ld or c) * 4 < 2 ** 31)
+            and h * w * (ld or c) * 4 < 2 ** 31 and _view16(cout if out_ld is None else out_ld, out_off)
+            and (res_ld is None or _view16(res_ld, res_off)))
 
 
 def pack_grouped_weights(w, groups):
@@ -189,13 +199,19 @@ WINO4_SMALL_MAX_CIN = int(os.environ.get('CSM_WINO4_SMALL_MAX_CIN', '512'))
 WINO4_SMALL_MIN_CH = int(os.environ.get('CSM_WINO4_SMALL_MIN_CH', '128'))      # narrower layers on small maps gain nothing at any batch
 
 
-def wino4_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ho, wo, ld=None):
+def wino4_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ho, wo, ld=None, out_ld=None, res_ld=None):
     """the F(2x2) layer class (3x3 / stride 1 / pad 1 / dense, cin % 32 == 0, cout % 64 == 0, 32-bit descriptor ranges) on maps of at
     least WINO4_MIN_PIXELS output pixels per sample -- and, round 6b, on SMALLER maps down to WINO4_SMALL_MIN_PIXELS (23 x 23) when
     128 <= cin <= WINO4_SMALL_MAX_CIN and cout >= 128: at batch 8 those layers run 1.4-1.8 x the direct kernels, and the K loop of one block tile
-    (cin / 4 steps) stays short enough for the row-split forms at batch 1 (profiles/r06_wino4_forms.txt).  Per-sample: batch invariant."""
+    (cin / 4 steps) stays short enough for the row-split forms at batch 1 (profiles/r06_wino4_forms.txt).  Per-sample: batch invariant.
+    out_ld / res_ld: channel pitch of the output / residual view (None: cout / no residual).  The epilogue addresses ONE sample of each
+    through a 32-bit buffer descriptor (csrc/wino4.hip::wino4_eligible): a view of 2 GiB or more lowers to F(2x2), whose epilogue uses
+    64-bit pointers.  Neither Winograd kernel needs more than 4-byte alignment of the output or the residual (single-float stores)."""
     ld = cin_g if ld is None else ld
     px = ho * wo
+    out_ld = cout if out_ld is None else out_ld
+    if ((px - 1) * out_ld + cout) * 4 >= 2 ** 31 or (res_ld is not None and ((px - 1) * res_ld + cout) * 4 >= 2 ** 31):
+        return False
     return (kh == 3 and kw == 3 and stride == 1 and pad == 1 and dil == 1 and groups == 1 and cin_g % 32 == 0 and cout % WINO_BN == 0
             and (px >= WINO4_MIN_PIXELS or (px >= WINO4_SMALL_MIN_PIXELS and WINO4_SMALL_MIN_CH <= cin_g <= WINO4_SMALL_MAX_CIN
                                             and cout >= WINO4_SMALL_MIN_CH))
@@ -334,9 +350,13 @@ class Program:
             out = self.buffer(x.n, ho, wo, cout)
         assert out.shape == (x.n, ho, wo, cout), (out.shape, (x.n, ho, wo, cout))
         stem = groups == 1 and cin_g == 4 and cout > 4        # k_conv_stem: (tap, channel)-packed K, csm_op.flags bit 1
-        wino4 = self.winograd and self.winograd4 and wino4_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ho, wo, ld=x.buf.c)
+        # a layer lowers to a form whose C++ predicate accepts its views (pitch and channel offset of the output and the residual included)
+        res_ld, res_off = (res.buf.c, res.coff) if res is not None and res_mode else (None, 0)
+        wino4 = self.winograd and self.winograd4 and wino4_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ho, wo, ld=x.buf.c,
+                                                                    out_ld=out.buf.c, res_ld=res_ld)
         wino = wino4 or (self.winograd and wino_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ho, wo, ld=x.buf.c))
-        gvalu = self.grouped_valu and grouped_valu_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ld=x.buf.c, h=x.h, w=x.w)
+        gvalu = self.grouped_valu and grouped_valu_eligible(kh, kw, stride, pad, dil, groups, cin_g, cout, ld=x.buf.c, h=x.h, w=x.w,
+                                                            out_ld=out.buf.c, out_off=out.coff, res_ld=res_ld, res_off=res_off)
         if stem:
             packed, sg, cin_sg, cout_sg = pack_stem_weights(w), 1, 4, cout
         elif gvalu:

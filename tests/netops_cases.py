@@ -1,6 +1,7 @@
-"""Case generators, plain references and one-op programs for the layer-program ops of csrc/netops.hip that are not convolutions on
-the matrix pipe: depthwise conv, max pool, bilinear / nearest resize, the element-wise ops and their activations, the ZoeDepth
-attractor and log-binomial ops, global average pool and the NCHW <-> NHWC transposes (csmconv::launch_netop).
+"""Case generators, plain references and one-op programs for the layer-program ops of csrc/netops.hip other than the convolutions
+on the matrix pipe and their relatives (those, layer by layer against float64, are tests/conv_cases.py): depthwise conv, max pool,
+bilinear / nearest resize, the element-wise ops and their activations, the ZoeDepth attractor and log-binomial ops, global average pool
+and the NCHW <-> NHWC transposes (csmconv::launch_netop).
 
 The references are numpy float64, or CPU torch float64 for what aten defines (F.conv2d with groups = c, F.max_pool2d, F.interpolate);
 nothing comes from the library's kernels or from the oracle.  Where an op rounds more than once the PLAIN FLOAT32 EVALUATION of the same

@@ -85,3 +85,57 @@ def test_oracle_is_indifferent_to_the_grouped_flag():
                                                             xp[:, gi * cg:(gi + 1) * cg, ky:ky + h, kx:kx + w])
     ref = np.maximum(ref + b.reshape(1, -1, 1, 1), 0.0)
     assert np.abs(outs[0] - ref).max() <= 2e-5
+
+
+# ---- the views decide too: a layer lowers to a form whose C++ predicate accepts its output and residual views -------------------------
+
+def _lower(n, h, w, cin, cout, groups=1, out_view=None, res_view=None, res_mode=1, in_view=None):
+    """a 3x3 / stride 1 / pad 1 layer whose views are (buffer channels, channel offset) slices -> the conv op.  Shapes only: nothing is
+    allocated but the zero weights"""
+    p = P.Program('views')
+    view = lambda c, v: p.buffer(n, h, w, c) if v is None else p.buffer(n, h, w, v[0]).slice(v[1], v[1] + c)
+    x, out = view(cin, in_view), view(cout, out_view)
+    res = None if res_view is None else view(cout, res_view)
+    p.conv(x, np.zeros((cout, cin // groups, 3, 3), np.float32), None, pad=1, groups=groups, res=res, res_mode=res_mode, out=out)
+    return p.ops[-1]
+
+
+def test_grouped_layer_with_an_unaligned_output_or_residual_view_takes_the_block_diagonal_form():
+    """csrc/grouped.hip::grouped_eligible: out.ld % 4 == 0, out.p and res.p 16-byte aligned, res.ld % 4 == 0 (float4 stores and loads).
+    The block-diagonal form runs on the tile kernels, whose epilogue (csm_conv.h::conv_tail, k_splitk_reduce) moves single floats"""
+    flagged = lambda o: (o['flags'], o['groups'], o['cin_g'], o['cout_g'])
+    vector, block_diagonal = (P.CONV_FLAG_GROUPED, 4, 8, 8), (0, 1, 32, 32)
+    assert flagged(_lower(1, 6, 7, 32, 32, 4)) == vector
+    assert flagged(_lower(1, 6, 7, 32, 32, 4, out_view=(40, 4))) == vector                     # cat.slice(4, 36) of 40 channels
+    assert flagged(_lower(1, 6, 7, 32, 32, 4, out_view=(40, 2))) == block_diagonal             # cat.slice(2, 34) of 40 channels
+    assert flagged(_lower(1, 6, 7, 32, 32, 4, out_view=(38, 4))) == block_diagonal             # a slice of a 38-channel buffer
+    assert flagged(_lower(1, 6, 7, 32, 32, 4, out_view=(38, 0))) == block_diagonal
+    assert flagged(_lower(1, 6, 7, 32, 32, 4, res_view=(40, 4))) == vector
+    assert flagged(_lower(1, 6, 7, 32, 32, 4, res_view=(40, 2))) == block_diagonal
+    assert flagged(_lower(1, 6, 7, 32, 32, 4, res_view=(38, 4))) == block_diagonal
+    assert flagged(_lower(1, 6, 7, 32, 32, 4, res_view=(38, 4), res_mode=0)) == vector         # a residual that is not added is not read
+    for n in (1, 8):                                                                           # never the batch
+        assert flagged(_lower(n, 6, 7, 32, 32, 4, out_view=(40, 2))) == block_diagonal
+
+
+def test_winograd4_layer_with_an_output_or_residual_view_of_2_gib_takes_f2x2():
+    """csrc/wino4.hip::wino4_eligible: ONE sample's output view and residual view under 2 GiB (the epilogue's 32-bit buffer
+    descriptors); F(2x2)'s epilogue uses 64-bit pointers (csrc/wino.hip), so the layer goes there.  Neither needs an aligned output:
+    both store single floats"""
+    old = (P.Program.winograd, P.Program.winograd4)
+    P.Program.winograd = P.Program.winograd4 = True
+    try:
+        px = 1000 * 1000
+        assert ((px - 1) * 500 + 64) * 4 < 2 ** 31 <= ((px - 1) * 600 + 64) * 4
+        flag = lambda **kw: _lower(kw.pop('n', 1), 1000, 1000, 64, 64, **kw)['flags']
+        assert flag() == P.CONV_FLAG_WINOGRAD4
+        assert flag(out_view=(500, 4)) == P.CONV_FLAG_WINOGRAD4 and flag(out_view=(600, 4)) == P.CONV_FLAG_WINOGRAD
+        assert flag(res_view=(500, 4)) == P.CONV_FLAG_WINOGRAD4 and flag(res_view=(600, 4)) == P.CONV_FLAG_WINOGRAD
+        assert flag(res_view=(600, 4), res_mode=0) == P.CONV_FLAG_WINOGRAD4
+        assert flag(n=4, out_view=(500, 4)) == P.CONV_FLAG_WINOGRAD4 and flag(n=4, out_view=(600, 4)) == P.CONV_FLAG_WINOGRAD    # per sample
+        assert flag(out_view=(70, 2)) == P.CONV_FLAG_WINOGRAD4 and flag(res_view=(70, 2)) == P.CONV_FLAG_WINOGRAD4             # any 4-byte alignment
+        assert flag(in_view=(600, 4)) == 0                                                     # (the input bound, as before: the direct chain)
+        P.Program.winograd4 = False
+        assert flag(out_view=(600, 2)) == P.CONV_FLAG_WINOGRAD
+    finally:
+        P.Program.winograd, P.Program.winograd4 = old

@@ -229,6 +229,27 @@ def test_zoedepth_head_vs_reference_text():
     assert out.min() > 0
 
 
+def test_zoedepth_head_has_no_layer_the_winograd_forms_could_take():
+    """the metric-bins head is 1x1 convolutions only (projectors, attractor and bin MLPs, the conditional log-binomial): forcing F(4x4)
+    -- or any size rule -- changes no op of it, so test_zoedepth_head_vs_reference_text IS its F(4x4) fixture; the 3x3 layers of the
+    depth model live in the DPT-BEiT program (tests/test_oracle_dpt_beit.py)"""
+    from cartoonsegmentation_amd import program as P
+    from cartoonsegmentation_amd.nets import build_zoe_head
+    from test_oracle_winograd4 import forced
+    H, W = 64, 96
+    sizes = [(H >> s, W >> s) for s in (5, 4, 3, 2, 1)]
+    progs = [build_zoe_head(SynthWeights('zoe.'), 1, H, W, sizes)]
+    with forced('f4'):
+        progs.append(build_zoe_head(SynthWeights('zoe.'), 1, H, W, sizes))
+    with forced('f4'):
+        progs.append(build_zoe_head(SynthWeights('zoe.'), 1, 384, 512, [(384 >> s, 512 >> s) for s in (5, 4, 3, 2, 1)]))       # the operating size
+    for prog in progs:
+        convs = [o for o in prog.ops if o['kind'] == P.OP_CONV]
+        assert len(convs) == 23 and all((o['kh'], o['kw'], o['flags']) == (1, 1, 0) for o in convs)
+    a, b = progs[0].serialise(), progs[1].serialise()
+    assert bytes(a[0]) == bytes(b[0]) and np.array_equal(a[2], b[2])
+
+
 def test_torch_cpu_interpreter_agrees_with_the_c_oracle():
     """oracle/nets_torch.py (the torch-CPU / oneDNN execution that bench.py times as `cpu_baseline`) runs the same lowered
     programs as the fmaf-chain C interpreter: outputs agree at fp32 round-off, so the timed baseline computes the real thing"""

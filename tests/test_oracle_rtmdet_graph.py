@@ -16,7 +16,9 @@ from cartoonsegmentation_amd import synth  # noqa: E402
 from cartoonsegmentation_amd.nets import build_rtmdet  # noqa: E402
 from cartoonsegmentation_amd.nets.rtmdet import RTMDetConfig  # noqa: E402
 from cartoonsegmentation_amd.weights import StateDictWeights  # noqa: E402
+from cartoonsegmentation_amd import program as P  # noqa: E402
 from oracle import nets as onets, rtmdet_torch as rt, segment as oseg  # noqa: E402
+from test_oracle_winograd4 import forced  # noqa: E402
 
 
 def _rel(a, b):
@@ -32,12 +34,30 @@ def _build(cfg, S):
     return model, rp, sd
 
 
-@pytest.mark.parametrize("name,cfg,S", [
-    ("l", RTMDetConfig(), 96),                                                        # RTMDet-Ins-L, the shipped detector
-    ("tiny", RTMDetConfig(deepen_factor=0.167, widen_factor=0.375, feat_channels=96), 128),
+def _f4_maps(rp):
+    """output map heights of the convs the lowering flagged F(4x4)"""
+    return [rp.prog.views[o['out']].buf.h for o in rp.prog.ops if o['kind'] == P.OP_CONV and o['flags'] & P.CONV_FLAG_WINOGRAD4]
+
+
+# arith: 'rule' = the shipped lowering rule, 'f4' = every eligible 3x3 layer forced to F(4x4).  Under the rule S = 96 and 128 lower every
+# layer to the direct chain; S = 192 is the smallest size (a multiple of 32) at which the rule itself puts neck and head layers on
+# F(4x4): their stride-8 maps are 24 x 24 = 576 >= WINO4_SMALL_MIN_PIXELS pixels with 256 channels.  Measured worst relative error
+# against the independent modules: rule S = 96 8.7e-7, forced F(4x4) S = 96 1.1e-6 (50 of 131 convs), rule S = 192 1.4e-6 (19 of 131).
+@pytest.mark.parametrize("name,cfg,S,arith", [
+    pytest.param("l", RTMDetConfig(), 96, 'rule', id="l-cfg0-96"),                    # RTMDet-Ins-L, the shipped detector
+    pytest.param("tiny", RTMDetConfig(deepen_factor=0.167, widen_factor=0.375, feat_channels=96), 128, 'rule', id="tiny-cfg1-128"),
+    pytest.param("l", RTMDetConfig(), 96, 'f4', id="l-96-f4"),
+    pytest.param("l", RTMDetConfig(), 192, 'rule', id="l-192-rule"),
 ])
-def test_lowered_graph_matches_independent_torch_modules(name, cfg, S):
-    model, rp, sd = _build(cfg, S)
+def test_lowered_graph_matches_independent_torch_modules(name, cfg, S, arith):
+    if arith == 'f4':
+        with forced('f4'):
+            model, rp, sd = _build(cfg, S)
+        assert len(_f4_maps(rp)) >= 40                                                # backbone, neck and head layers at every level
+    else:
+        model, rp, sd = _build(cfg, S)
+        # the rule flags nothing at the small sizes; at 192 the 24 x 24 neck and head layers (and the 96 x 96 backbone stage) take F(4x4)
+        assert (24 in _f4_maps(rp) and len(_f4_maps(rp)) >= 10) if S == 192 else not _f4_maps(rp)
     # mmdet's module sharing is visible in the state_dict: reg tower = cls tower, cls convs tied across levels, BNs per level
     assert torch.equal(sd['bbox_head.reg_convs.1.0.conv.weight'], sd['bbox_head.cls_convs.0.0.conv.weight'])
     assert torch.equal(sd['bbox_head.reg_convs.2.1.bn.weight'], sd['bbox_head.cls_convs.2.1.bn.weight'])
