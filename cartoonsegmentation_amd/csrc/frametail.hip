@@ -11,7 +11,10 @@
 //   csm_colorize_gray_r_dev  colorize(value, cmap='gray_r') reading vmin / vmax from device memory, LUT applied in the kernel.
 //   csm_bokeh_depth_auto  the depth map of bokeh_blur (utils/effects.py:146-163): its three scalar reductions run over the 256-bin
 //                         histogram of the uint8 depth (max d; min and max of dmax - |d - focal| only depend on which values occur).
-// All integer / order work: bit-exact with the sorted formulation (same elements selected), asserted in tests/test_gpu_kenburns.py.
+//   csm_colorize_stats / csm_bokeh_prep  the two fused kernels of csm_kenburns_frame (colourise + histogram + bokeh statistics;
+//                         bokeh depth plane + highlights) on their own, through the launch helpers the frame call uses.
+// All integer / order work: bit-exact with the sorted formulation (same elements selected), asserted in tests/test_gpu_kenburns.py
+// and, kernel by kernel at edge shapes, in tests/test_gpu_frametail.py.
 #include "csm_common.h"
 
 namespace {
@@ -169,6 +172,10 @@ __global__ __launch_bounds__(kBlock) void k_sel_top16(const float *__restrict__ 
     for (int i = tid; i < kWin; i += kBlock) hf[i] = 0u;
     unsigned *gx = g + (int64_t)xcd_id() * kHistWords;                    // this XCD's copy of the pass-1 tables
     hc[tid] = 0u;
+    // a rank that no bin holds (possible only in the poisoned state below, when the counts add up to LESS than n) must still index
+    // inside the tables: sbin is an index into them
+    if (tid < 4) { sbin[tid] = 0u; sbefore[tid] = 0u; }
+    if (tid < 2) res2[tid] = 0u;
     // window: centred on the block's first element
     const int64_t first = (int64_t)blockIdx.x * kBlock * 4;
     const unsigned d_first = ordered_key(v[first < n ? first : 0]) >> 16;
@@ -513,6 +520,40 @@ extern "C" int csm_bokeh_depth_auto(const uint8_t *depth_u8, float *out, int64_t
     return csm::check_launch("k_bokeh_depth_dev");
 }
 
+// ---- the two fused kernels of the frame loop: one launch helper each, shared by csm_kenburns_frame and the stand-alone entry points ----
+namespace {
+// scratch: a csm_bokeh_depth_scratch_bytes() buffer -- stats3 at +0, the ticket at +48, hist256 ([kXcd][256]) at +64; ticket and
+// hist256 zero on entry, left zero
+inline int launch_colorize_stats(const float *value, uint8_t *out_u8, int64_t n, const float *vmm_dev, const uint8_t *lut256_host, float focal_plane,
+                                 void *scratch, void *stream) {
+    Lut256 lut;
+    for (int i = 0; i < 256; ++i) lut.v[i] = lut256_host[i];
+    float *stats3 = (float *)scratch;
+    unsigned *ticket = (unsigned *)((char *)scratch + 48), *hist256 = (unsigned *)((char *)scratch + 64);   // [kXcd][256]
+    const unsigned blocks = (unsigned)csm::cdiv(csm::cdiv(n, 4), kBlock);
+    k_colorize_stats<<<blocks < 256u ? blocks : 256u, kBlock, 0, (hipStream_t)stream>>>(value, out_u8, n, vmm_dev, lut, hist256, ticket, focal_plane, stats3);
+    return csm::check_launch("k_colorize_stats");
+}
+inline int launch_bokeh_prep(const uint8_t *depth_u8, const uint8_t *img_u8, float *dm, float *hi, int64_t n, float focal_plane, const float *stats3_dev,
+                             float lightness, void *stream) {
+    const unsigned blocks = (unsigned)csm::cdiv(csm::cdiv(n, 4), kBlock);
+    k_bokeh_prep<<<blocks < 1024u ? blocks : 1024u, kBlock, 0, (hipStream_t)stream>>>(depth_u8, img_u8, dm, hi, n, focal_plane, stats3_dev, lightness);
+    return csm::check_launch("k_bokeh_prep");
+}
+}  // namespace
+
+extern "C" int csm_colorize_stats(const float *value, uint8_t *out_u8, int64_t n, const float *vmin_vmax_dev, const uint8_t *lut256_host,
+                                  float focal_plane, void *scratch, void *stream) {
+    CSM_REQUIRE(value && out_u8 && vmin_vmax_dev && lut256_host && scratch && n > 0);
+    return launch_colorize_stats(value, out_u8, n, vmin_vmax_dev, lut256_host, focal_plane, scratch, stream);
+}
+
+extern "C" int csm_bokeh_prep(const uint8_t *depth_u8, const uint8_t *img_u8, float *dm, float *hi, int64_t n, float focal_plane,
+                              const float *stats3_dev, float lightness, void *stream) {
+    CSM_REQUIRE(depth_u8 && img_u8 && dm && hi && stats3_dev && n > 0);
+    return launch_bokeh_prep(depth_u8, img_u8, dm, hi, n, focal_plane, stats3_dev, lightness, stream);
+}
+
 // ---- focal plane of the depth of field: the largest per-instance MEDIAN of the colourised depth (kenburns_effect.py:1045-1056) ----
 // The reference gathers depth_rendered[mask] on the host and calls np.median per instance.  Values are uint8, so a 256-bin histogram
 // per instance holds everything: the two middle order statistics come from its prefix sums, np.median's even-count rule (mean of
@@ -615,17 +656,8 @@ extern "C" int csm_kenburns_frame(const float *pts, const float *rgb, const floa
         // colorize(depth, cmap='gray_r')[..., 0] with the 2nd / 85th percentiles (zoedepth/utils/misc.py:97-135)
         rc = csm_percentile_pair(rdepth, P, 2.0, 85.0, s.vmm, s.sel, stream); if (rc) return rc;
         // colourised depth + its histogram + the three scalars of the bokeh depth map (one launch), then depth plane + highlights (one launch)
-        {
-            Lut256 lut;
-            for (int i = 0; i < 256; ++i) lut.v[i] = gray_r_lut256_host[i];
-            float *stats3 = (float *)s.bdepth;
-            unsigned *ticket = (unsigned *)((char *)s.bdepth + 48), *hist256 = (unsigned *)((char *)s.bdepth + 64);   // [kXcd][256]
-            const unsigned blocks = (unsigned)csm::cdiv(csm::cdiv(P, 4), kBlock);
-            k_colorize_stats<<<blocks < 256u ? blocks : 256u, kBlock, 0, (hipStream_t)stream>>>(rdepth, s.depth_u8, P, s.vmm, lut, hist256, ticket, focal_plane, stats3);
-            rc = csm::check_launch("k_colorize_stats"); if (rc) return rc;
-            k_bokeh_prep<<<blocks < 1024u ? blocks : 1024u, kBlock, 0, (hipStream_t)stream>>>(s.depth_u8, frame_u8, s.dm, s.hi, P, focal_plane, stats3, lightness);
-            rc = csm::check_launch("k_bokeh_prep"); if (rc) return rc;
-        }
+        rc = launch_colorize_stats(rdepth, s.depth_u8, P, s.vmm, gray_r_lut256_host, focal_plane, s.bdepth, stream); if (rc) return rc;
+        rc = launch_bokeh_prep(s.depth_u8, frame_u8, s.dm, s.hi, P, focal_plane, (const float *)s.bdepth, lightness, stream); if (rc) return rc;
         const double PI = 3.14159265358979323846;
         rc = csm_bokeh_pass(s.hi, s.dm, s.pa, H, W, num_samples, 0.0f, 1.0f, stream); if (rc) return rc;
         rc = csm_bokeh_pass(s.pa, s.dm, s.pb, H, W, num_samples, (float)cos(-PI / 6), (float)sin(-PI / 6), stream); if (rc) return rc;

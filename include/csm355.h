@@ -1013,17 +1013,28 @@ int csm_colorize_gray_r(const float *value, uint8_t *out, int64_t n, float vmin,
  *   3-pass (16 + 8 + 8 bit) radix select instead of a sort, three launches; scratch = csm_percentile_scratch_bytes() device bytes, ZEROED
  *   ONCE by the caller (every call leaves the counting tables it needs next time cleared) and used by one stream at a time.  If a call
  *   finds the tables NOT in that state (e.g. after an aborted launch) its counts do not add up to n: out2 becomes NaN, for that call and
- *   every later one, until the caller zeroes the scratch again -- never a plausible wrong percentile.
+ *   every later one, until the caller zeroes the scratch again -- never a plausible wrong percentile.  NaN inputs are OUTSIDE the
+ *   contract (the select orders the bit patterns, numpy propagates NaN); +-inf, +-0 and denormals are inside it.
  * csm_colorize_gray_r_dev: csm_colorize_gray_r with vmin / vmax read from device memory and the matplotlib byte LUT (256 HOST
  *   bytes, index -> grey level) applied in the kernel.
  * csm_bokeh_depth_auto: csm_bokeh_depth with dmax / mn / mx2 derived on the device from the histogram of depth_u8; scratch =
- *   csm_bokeh_depth_scratch_bytes() device bytes. */
+ *   csm_bokeh_depth_scratch_bytes() device bytes.
+ * csm_colorize_stats: the frame loop's fused form of csm_colorize_gray_r_dev + the three scalars of csm_bokeh_depth_auto (one launch,
+ *   the one csm_kenburns_frame makes): out_u8 as csm_colorize_gray_r_dev; scratch = csm_bokeh_depth_scratch_bytes() device bytes,
+ *   ZEROED ONCE by the caller and used by one stream at a time: {dmax, mn, mx2} of out_u8 for focal_plane land in its first three
+ *   floats, its ticket (+48) and per-XCD histograms (+64) are left zero by every call.
+ * csm_bokeh_prep: the frame loop's fused form of csm_bokeh_depth + csm_bokeh_highlight (one launch): dm [n] from depth_u8 [n] and
+ *   stats3_dev = {dmax, mn, mx2} in DEVICE memory, hi [3n] = (img_u8 [3n] / 255)^lightness. */
 size_t csm_percentile_scratch_bytes(void);
 int csm_percentile_pair(const float *value, int64_t n, double q_lo, double q_hi, float *out2, void *scratch, void *stream);
 int csm_colorize_gray_r_dev(const float *value, uint8_t *out, int64_t n, const float *vmin_vmax_dev, const uint8_t *lut256_host,
                             void *stream);
 size_t csm_bokeh_depth_scratch_bytes(void);
 int csm_bokeh_depth_auto(const uint8_t *depth_u8, float *out, int64_t n, float focal_plane, void *scratch, void *stream);
+int csm_colorize_stats(const float *value, uint8_t *out_u8, int64_t n, const float *vmin_vmax_dev, const uint8_t *lut256_host,
+                       float focal_plane, void *scratch, void *stream);
+int csm_bokeh_prep(const uint8_t *depth_u8, const uint8_t *img_u8, float *dm, float *hi, int64_t n, float focal_plane,
+                   const float *stats3_dev, float lightness, void *stream);
 
 /* One output frame of KenBurnsPipeline.process_kenburns (kenburns_effect.py:1027-1072) in ONE call: csm_warp_frame_tiled
  * [-> csm_percentile_pair(2, 85) -> csm_colorize_gray_r_dev -> csm_bokeh_depth_auto -> csm_bokeh_highlight -> 2 x csm_bokeh_pass ->

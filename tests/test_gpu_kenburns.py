@@ -547,8 +547,8 @@ def test_default_depth_estimator_pipeline():
 
 
 def test_device_percentiles_and_bokeh_stats_are_exact():
-    """csm_percentile_pair (2-pass 16 + 16 bit radix select, no sort, no host sync; one scratch re-used by every call: each call
-    must leave its counting tables cleared) == the order statistics of the sorted array for awkward inputs (negatives, signed zeros,
+    """csm_percentile_pair (3-pass 16 + 8 + 8 bit radix select in three launches, no sort, no host sync; one scratch re-used by every
+    call: each call must leave its counting tables cleared) == the order statistics of the sorted array for awkward inputs (negatives, signed zeros,
     heavy ties, tiny / huge magnitudes, two far-apart clusters, a constant plane, a smooth ramp, an unaligned plane), and
     csm_bokeh_depth_auto == csm_bokeh_depth fed with the
     host-side reductions"""
